@@ -22,6 +22,11 @@ batch descriptors in, ~B*88 bytes, inside the step).
         the window identically over its replica of the node state (strong
         scaling: the total node count is fixed).
 
+A plain run sets up, warms up, times the steps and prints the headline line
+(value, ms_per_step, the timed run's own device / host times, config). With
+--dump-outputs DIR it also writes the last timed step's results (seeded inputs:
+the same arguments give the same arrays). Everything below runs only with --full.
+
 Roofline: bound "hbm"; achieved = algorithmic bytes per launch / kernel time,
 with SURVEY.md 8(d)'s 60 B/node/pod for this predicate+priority set
 (resources 32 + ports 8 + PD 8 + labels 8 + spread count 4) x nodes x pods per
@@ -288,6 +293,17 @@ def main():
                          "cpu_baseline legs start from the same state (the prefix's placements added as pods)")
     ap.add_argument("--no-stages", action="store_true",
                     help="skip the resolver's per-stage cycle breakdown (a second, untimed run with KSG_DEBUG=8)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also everything beside the headline figure: the roofline and "
+                         "filter_score views (with the untimed KSG_FUSED=0 side run), the latency view and its "
+                         "stage breakdown, the cpu_baseline legs and their decision check (--cpu-seconds, "
+                         "--no-cpu-baseline, --no-stages and --traffic-json act only here); a plain run sets up, "
+                         "warms up, times the steps and prints the headline fields")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float64): placements.npy, the step's node index per pod (-1: no node "
+                         "fits), and rng_state.npy, the tie-break generator's state after it as [high, low] "
+                         "32-bit halves")
     args = ap.parse_args()
 
     # HIP events around every 8th window launch (the library's default is every 4th): each event
@@ -302,16 +318,18 @@ def main():
     pre = max(0, args.prefix_pods)
     n_pods = pre + (args.warmup + args.steps) * args.batch
 
-    from kubernetes_amd import ingest, workload
+    from kubernetes_amd import ingest, podstream, workload
     from kubernetes_amd.engine import DeviceScheduler, PodBatch
 
     t0 = time.time()
-    w = workload.build(wl, n_nodes=args.nodes, n_pods=n_pods)
+    # (the pods as arrays straight from the seeded stream: the api-object path, ~20 us a pod, would be
+    # most of a long run's set-up)
+    w = workload.build(wl, n_nodes=args.nodes, n_pods=n_pods, pod_stream=True)
     it = ingest.Interner()
     for k in w.config.label_keys():
         it.key_id(k)
     view = ingest.ClusterView(w.nodes, w.services, it)
-    batch = ingest.ingest_pods(view, w.pods, aff_labels=w.config.affinity_labels())
+    batch = podstream.ingest_stream(view, w.stream, aff_labels=w.config.affinity_labels())
     cfg = w.config.compile(it.key_id)
     n_nodes = view.arrays.n_nodes
     ext = None  # (--extensions) the context's ExtConfig and node arrays
@@ -385,9 +403,11 @@ def main():
         outs.append(o)
 
     def barrier():
+        # (one rank: every batch has returned its results to the host, so nothing is in flight
+        # on the device, and torch, whose import can take a minute, is not loaded)
         if dist is not None:
             dist.barrier()
-        _torch_sync()
+            _torch_sync()
 
     # the library's per-batch diagnostics (device ms, kernel ms from the HIP
     # events, window stats, host phases) accumulate in the context: read once
@@ -418,6 +438,56 @@ def main():
     value = pods_timed / elapsed
 
     if rank != 0:
+        sched.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    if args.dump_outputs:
+        # the last timed step's return values (every rank holds the same ones): int32 node indices
+        # and the uint64 generator state in halves, both exact in float64
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "placements.npy"), outs[-1].astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "rng_state.npy"),
+                np.array([rng >> 32, rng & 0xFFFFFFFF], np.float64))
+
+    xname = "RCCL" if args.transport == "rccl" else "host-staged gloo"
+    line = {
+        "metric": "pods scheduled/sec",
+        "value": value,
+        "unit": "pods/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "device_ms_per_step": float(np.mean(kern_ms)) if kern_ms else None,
+        "host_us_per_step": {k_: round(v_ / args.steps, 1) for k_, v_ in host_us.items()},
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "int64",
+        "data": "synthetic (seeded splitmix64 scheduler_perf-style cluster; SURVEY.md 8(d))",
+        "config": {"workload": f"{wl}: {n_nodes} nodes, {n_pods} pods, "
+                               + ("DefaultProvider" if wl in ("config2", "config3", "config5") else wl)
+                               + ((" + extension filters (taints/tolerations; scoring extensions off; parity "
+                                   "unpinned)" if args.ext_filters_only and args.ext_taints_only else
+                                   " + extension filters (taints/tolerations, GPU/FPGA counts; scoring "
+                                   "extensions off; parity unpinned, window path)" if args.ext_filters_only else
+                                   " + extensions (taints/tolerations, GPU/FPGA counts, TaintToleration, "
+                                   "BalancedResourceAllocation; parity unpinned)") if ext else ""),
+                   "nodes": n_nodes, "pods_per_step": args.batch,
+                   "prefix_pods": pre, "placed_in_prefix": int((out_pre >= 0).sum()),
+                   "timed_pods": [pre + args.warmup * args.batch, n_pods],
+                   "placed_in_timed": int((timed >= 0).sum()), "fit_errors_in_timed": int((timed == -1).sum()),
+                   "snapshots_in_timed": wstats,
+                   "exchange": None if world == 1 else args.transport,
+                   "parallelism": ("speculative windows: all-CU snapshot scoring + in-order exact resolver"
+                                   if kk["launches"] else "single workgroup persistent kernel") if world == 1
+                   else (f"node-sharded x{world}: shard scoring, {xname} all-gather per window, replicated resolver"
+                         if kk["launches"] else f"node-sharded x{world}, {xname} all-gather per pod")},
+    }
+    if not args.full:  # a plain run: the headline figure only
+        print(json.dumps(line), flush=True)
         sched.close()
         if dist is not None:
             dist.destroy_process_group()
@@ -638,45 +708,7 @@ def main():
                                      "decisions_identical": mt_agree, "pods_checked": done_m,
                                      "whole_run_checked": bool(mt_all and mt_agree)}}
 
-    xname = "RCCL" if args.transport == "rccl" else "host-staged gloo"
-    line = {
-        "metric": "pods scheduled/sec",
-        "value": value,
-        "unit": "pods/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "device_ms_per_step": float(np.mean(kern_ms)) if kern_ms else None,
-        "host_us_per_step": {k_: round(v_ / args.steps, 1) for k_, v_ in host_us.items()},
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "int64",
-        "data": "synthetic (seeded splitmix64 scheduler_perf-style cluster; SURVEY.md 8(d))",
-        "config": {"workload": f"{wl}: {n_nodes} nodes, {n_pods} pods, "
-                               + ("DefaultProvider" if wl in ("config2", "config3", "config5") else wl)
-                               + ((" + extension filters (taints/tolerations; scoring extensions off; parity "
-                                   "unpinned)" if args.ext_filters_only and args.ext_taints_only else
-                                   " + extension filters (taints/tolerations, GPU/FPGA counts; scoring "
-                                   "extensions off; parity unpinned, window path)" if args.ext_filters_only else
-                                   " + extensions (taints/tolerations, GPU/FPGA counts, TaintToleration, "
-                                   "BalancedResourceAllocation; parity unpinned)") if ext else ""),
-                   "nodes": n_nodes, "pods_per_step": args.batch,
-                   "prefix_pods": pre, "placed_in_prefix": int((out_pre >= 0).sum()),
-                   "timed_pods": [pre + args.warmup * args.batch, n_pods],
-                   "placed_in_timed": int((timed >= 0).sum()), "fit_errors_in_timed": int((timed == -1).sum()),
-                   "snapshots_in_timed": wstats,
-                   "exchange": None if world == 1 else args.transport,
-                   "parallelism": ("speculative windows: all-CU snapshot scoring + in-order exact resolver"
-                                   if kk["launches"] else "single workgroup persistent kernel") if world == 1
-                   else (f"node-sharded x{world}: shard scoring, {xname} all-gather per window, replicated resolver"
-                         if kk["launches"] else f"node-sharded x{world}, {xname} all-gather per pod")},
-        "roofline": roofline,
-        "filter_score": filter_score,
-        "latency": latency,
-        "cpu_baseline": cpu,
-    }
+    line.update({"roofline": roofline, "filter_score": filter_score, "latency": latency, "cpu_baseline": cpu})
     print(json.dumps(line), flush=True)
     sched.close()
     if dist is not None:

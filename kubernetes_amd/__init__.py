@@ -12,5 +12,6 @@ host-side mirror of the reference's algorithm API:
   engine       one libkschedgpu.so context (DeviceScheduler)
   api/resource/labels   the pkg/api, resource.Quantity and labels subset the path reads
   workload     seeded synthetic scheduler_perf-style clusters (BASELINE configs)
+  podstream    the workload's pods drawn and interned as arrays (no api objects; bench.py's set-up)
 """
 __version__ = "0.1.0"

@@ -51,6 +51,7 @@ class Workload:
     services: List[Service]
     config: factory.SchedulerConfig
     existing: List[Pod]
+    stream: Optional[object] = None  # (build(pod_stream=True)) the pods as a podstream.PodStream, pods empty
 
 
 def make_nodes(n: int, rng: _SM, dense_labels: int = 0) -> List[Node]:
@@ -128,8 +129,10 @@ def config4() -> factory.SchedulerConfig:
     return factory.create_from_config(policy)
 
 
-def build(name: str, n_nodes: Optional[int] = None, n_pods: Optional[int] = None, seed: int = WORKLOAD_SEED) -> Workload:
-    """BASELINE.json configs: 'config1'..'config5' (sizes overridable)."""
+def build(name: str, n_nodes: Optional[int] = None, n_pods: Optional[int] = None, seed: int = WORKLOAD_SEED,
+          pod_stream: bool = False) -> Workload:
+    """BASELINE.json configs: 'config1'..'config5' (sizes overridable). pod_stream: leave the pods
+    undrawn, as Workload.stream for podstream.ingest_stream (the same pods without the api objects)."""
     rng = _SM(seed)
     if name == "config1":
         nn, npods, cfg, dense = 500, 1000, config1(), 0
@@ -146,6 +149,12 @@ def build(name: str, n_nodes: Optional[int] = None, n_pods: Optional[int] = None
     nn = nn if n_nodes is None else n_nodes
     npods = npods if n_pods is None else n_pods
     nodes = make_nodes(nn, rng, dense_labels=dense)
+    if pod_stream:
+        from .podstream import PodStream
+
+        cfg.max_conflict_keys = 4096
+        return Workload(name, nodes, [], make_services(), cfg, [],
+                        PodStream(rng.s, npods, dense_sel=dense, resources_only=name == "config1"))
     pods = make_pods(npods, rng, dense_sel=dense)
     if name == "config1":  # resources only: no ports / PDs / selectors matter, keep them off
         pods = [Pod(metadata=p.metadata, spec=PodSpec(containers=[Container(name="c", resources=p.spec.containers[0].resources)]))

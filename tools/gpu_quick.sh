@@ -9,6 +9,7 @@ if [ -z "$NOTESTS" ]; then
     > gpurun_out/${TAG}_tests.log 2>&1 || { tail -40 gpurun_out/${TAG}_tests.log; exit 1; }
   tail -2 gpurun_out/${TAG}_tests.log
 fi
+BENCH_ARGS="--full ${BENCH_ARGS}"  # (the latency / roofline fields and stages printed below)
 for spec in "$@"; do
   n=${spec%%:*}; envs=${spec#*:}
   ( IFS=','; for kv in $envs; do [ -n "$kv" ] && export "$kv"; done; unset IFS

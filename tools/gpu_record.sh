@@ -19,6 +19,7 @@ case "$STEP" in
     tail -3 gpurun_out/${TAG}_smoke.log ;;
   bench)
     WL=$1; shift
+    set -- --full "$@"  # (the roofline, latency and cpu_baseline fields the summary below prints)
     timeout -k 10 400 python bench.py --workload $WL "$@" > gpurun_out/${TAG}_bench_$WL.json 2> gpurun_out/${TAG}_bench_$WL.err \
       || { tail gpurun_out/${TAG}_bench_$WL.err; exit 1; }
     python - gpurun_out/${TAG}_bench_$WL.json <<'PY'
@@ -35,13 +36,13 @@ PY
     OUT=gpurun_out/prof_${TAG}_$WL
     mkdir -p $OUT
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o run -- \
-      python3 bench.py --no-cpu-baseline --no-stages --workload $WL "$@" > $OUT/bench_kt.json 2> $OUT/bench_kt.err \
+      python3 bench.py --full --no-cpu-baseline --no-stages --workload $WL "$@" > $OUT/bench_kt.json 2> $OUT/bench_kt.err \
       || { tail $OUT/bench_kt.err; exit 1; }
     timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- \
-      python3 bench.py --no-cpu-baseline --no-stages --workload $WL "$@" > $OUT/bench_fetch.json 2> $OUT/bench_fetch.err \
+      python3 bench.py --full --no-cpu-baseline --no-stages --workload $WL "$@" > $OUT/bench_fetch.json 2> $OUT/bench_fetch.err \
       || { tail $OUT/bench_fetch.err; exit 1; }
     timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o run -- \
-      python3 bench.py --no-cpu-baseline --no-stages --workload $WL "$@" > $OUT/bench_write.json 2> $OUT/bench_write.err \
+      python3 bench.py --full --no-cpu-baseline --no-stages --workload $WL "$@" > $OUT/bench_write.json 2> $OUT/bench_write.err \
       || { tail $OUT/bench_write.err; exit 1; }
     NN=$(python3 -c "import json,sys; print(json.loads(open('$OUT/bench_kt.json').read().strip().splitlines()[-1])['config']['nodes'])")
     mv $OUT/fetch/*/run_counter_collection.csv $OUT/fetch/ 2>/dev/null; mv $OUT/write/*/run_counter_collection.csv $OUT/write/ 2>/dev/null
@@ -58,7 +59,7 @@ PY
     WL=$1; shift
     OUT=gpurun_out/sq_${TAG}_$WL
     timeout -s KILL 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY \
-      --output-format csv -d $OUT -o run -- python3 bench.py --no-cpu-baseline --no-stages --workload $WL --steps 3 --warmup 1 "$@" \
+      --output-format csv -d $OUT -o run -- python3 bench.py --full --no-cpu-baseline --no-stages --workload $WL --steps 3 --warmup 1 "$@" \
       > $OUT.json 2> $OUT.err || { tail $OUT.err; exit 1; }
     ls $OUT ;;
   *) echo "unknown step $STEP"; exit 2 ;;

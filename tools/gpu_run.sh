@@ -19,6 +19,7 @@ for step in "$@"; do
       tail -2 gpurun_out/tests_$k.log ;;
     kt)
       tag=$1; shift
+      set -- --full "$@"  # (with the KSG_FUSED=0 side run, as the traces on record)
       mkdir -p gpurun_out/kt_$tag
       timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d gpurun_out/kt_$tag -o run -- \
         python3 bench.py --no-cpu-baseline --no-stages "$@" > gpurun_out/kt_$tag/bench.json 2> gpurun_out/kt_$tag/bench.err \
@@ -29,6 +30,7 @@ for step in "$@"; do
       bash tools/gpu_ab_trees.sh $tag "$@" || exit 1 ;;
     bench)
       tag=$1; shift
+      set -- --full "$@"
       timeout -k 10 400 python bench.py "$@" > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.err \
         || { tail gpurun_out/bench_$tag.err; exit 1; }
       tail -c 600 gpurun_out/bench_$tag.json ;;

@@ -10,9 +10,9 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd "$R"
 timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o run -- \
-  python3 bench.py --no-cpu-baseline "$@" > "$OUT/bench_kt.log" 2>&1
+  python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/bench_kt.log" 2>&1
 timeout -s KILL 180 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -o run -- \
-  python3 bench.py --no-cpu-baseline "$@" > "$OUT/bench_fetch.log" 2>&1
+  python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/bench_fetch.log" 2>&1
 timeout -s KILL 180 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -o run -- \
-  python3 bench.py --no-cpu-baseline "$@" > "$OUT/bench_write.log" 2>&1
+  python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/bench_write.log" 2>&1
 find "$OUT" -name '*.csv' | sort

@@ -8,4 +8,4 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd "$R"
 timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o run -- \
-  python3 bench.py --no-cpu-baseline "$@" > "$OUT/bench_kt.log" 2>&1
+  python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/bench_kt.log" 2>&1
