@@ -112,7 +112,12 @@ typedef struct ksg_config {
    * (generic_scheduler.go:145-159). While 10 * sum|w| + |w_equal| < 2^30 the
    * window path runs with int32 scores (any number of ServiceAntiAffinity
    * priorities, any shard size up to 131,072 nodes); otherwise every batch takes
-   * the exact kernels with int64 (wrapping) combined scores. */
+   * the exact kernels with int64 (wrapping) combined scores. That bound takes
+   * every priority's score to lie in [0, 10]; calculateScore (priorities.go:27-37)
+   * leaves the range with a negative capacity, a capacity past 2^63 / 10 (its x10
+   * wraps) or a negative requested total, so a node list or a pod that can produce
+   * one of these also puts the context on the int64 kernels, until the next
+   * ksg_set_cluster. */
   int64_t w_least_requested;    /* LeastRequestedPriority weight, 0 = absent/skipped    */
   int64_t w_service_spreading;  /* ServiceSpreadingPriority weight                       */
   int64_t w_equal;              /* EqualPriority weight (DefaultProvider: 0, skipped)    */

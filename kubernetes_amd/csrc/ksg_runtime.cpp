@@ -256,6 +256,14 @@ struct ksg_ctx {
   std::unordered_set<uint64_t> dfr_uids;
   int64_t dfr_sum = 0;   // sum of the deferred pods' requests (cpu + memory), capped
   bool dfr_neg = false;  // a deferred pod has a negative request
+  // calculateScore (priorities.go:27-37) stays in [0, 10] only while capacities lie in
+  // [0, 2^63 / 10] and requested totals are non-negative; score_bound() assumes that range.
+  // lr_wild: this node list, or a pod seen since ksg_set_cluster, can take a LeastRequested
+  // term out of it (a negative capacity or one whose x10 wraps, a negative request, a total
+  // that wraps): the int64 score kernels serve the context from then on (KsgDev.wide)
+  bool lr_wild = false;
+  int64_t used_hi = 0;                // the largest committed total the mirror has held
+  unsigned __int128 dfr_req = 0;      // requests of batches whose commits are not in the mirror yet
 
   // extensions (ksg_set_extensions; exact kernels, one rank, parity unpinned)
   bool ext_on = false;
@@ -469,6 +477,7 @@ int mirror_add(ksg_ctx* c, uint32_t h, const ksg_pod* p, const uint32_t* ids, bo
   if (h < c->N) {
     c->used_c[h] = (int64_t)((uint64_t)c->used_c[h] + (uint64_t)r.cpu);
     c->used_m[h] = (int64_t)((uint64_t)c->used_m[h] + (uint64_t)r.mem);
+    c->used_hi = std::max(c->used_hi, std::max(c->used_c[h], c->used_m[h]));
     if (c->mu_neg || c->used_c[h] < 0 || c->used_m[h] < 0) c->mu_dirty = true;
     else c->mu_max = std::max(c->mu_max, std::max(c->used_c[h], c->used_m[h]));
     if (emit) {
@@ -509,6 +518,7 @@ int mirror_add(ksg_ctx* c, uint32_t h, const ksg_pod* p, const uint32_t* ids, bo
 void reset_mirror(ksg_ctx* c) {
   c->used_c.assign(c->N, 0);
   c->mu_dirty = true;
+  c->used_hi = 0;
   c->used_m.assign(c->N, 0);
   c->sc_used.assign((size_t)c->ext.n_scalar * c->N, 0);
   c->ext_scalar.clear();
@@ -802,7 +812,8 @@ bool use_window(ksg_ctx* c, const ksg_pod* pods, uint32_t n) {
   int64_t sum = c->dfr_sum;
   for (uint32_t i = 0; i < n; ++i) {
     if (pods[i].milli_cpu < 0 || pods[i].memory < 0) return false;
-    sum += std::min<int64_t>(pods[i].milli_cpu + pods[i].memory, lim);
+    // (each operand clamped first: two requests of 2^62 overflow the signed add)
+    sum += std::min<int64_t>(std::min<int64_t>(pods[i].milli_cpu, lim) + std::min<int64_t>(pods[i].memory, lim), lim);
     if (sum > lim) return false;
   }
   return mu + sum <= lim;
@@ -833,6 +844,7 @@ void drop_deferred(ksg_ctx* c) {
   c->dfr_out.clear();
   c->dfr_uids.clear();
   c->dfr_sum = 0;
+  c->dfr_req = 0;
   c->dfr_neg = false;
 }
 
@@ -1132,6 +1144,37 @@ int srv_stop(ksg_ctx* c) {
   // (a pending begin served by the server stays pending: its commit picks the node from
   // srv_tw on the host and posts the COMMIT to a relaunched server)
   HIPCHK(c, hipStreamSynchronize(c->st));
+  return KSG_OK;
+}
+
+// int64 combined scores (the exact kernels; the window path and the resident servers are
+// int32): once a |score| could reach KSG_SCORE_BOUND by the weights, or a LeastRequested
+// term can leave the [0, 10] that bound assumes
+void set_wide(ksg_ctx* c) {
+  c->dev.wide = score_bound(c->cfg, c->ext.w_taint_toleration, c->ext.w_balanced) + c->static_mag >=
+                    (unsigned __int128)KSG_SCORE_BOUND ||
+                (c->lr_wild && c->cfg.w_least_requested != 0);
+}
+
+// Pods about to be filtered, scored or committed. A negative request, or a requested total that could pass 2^63 - 1 and wrap
+// negative, takes calculateScore out of [0, 10]: the context turns to the int64 kernels
+// (the servers leave the stream and decline it from here on) until ksg_set_cluster.
+int note_requests(ksg_ctx* c, const ksg_pod* pods, uint32_t n) {
+  if (c->lr_wild || c->cfg.w_least_requested == 0) return KSG_OK;
+  bool wild = c->used_hi < 0;
+  unsigned __int128 sum = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    wild |= pods[i].milli_cpu < 0 || pods[i].memory < 0;
+    if (!wild) sum += (uint64_t)std::max(pods[i].milli_cpu, pods[i].memory);
+  }
+  wild = wild || (unsigned __int128)(uint64_t)std::max<int64_t>(c->used_hi, 0) + c->dfr_req + sum >
+                     (unsigned __int128)INT64_MAX;
+  if (!wild) return KSG_OK;
+  c->lr_wild = true;
+  if (!c->dev.wide) {
+    if (int rc = srv_stop(c)) return rc;
+    set_wide(c);
+  }
   return KSG_OK;
 }
 
@@ -1590,9 +1633,11 @@ int ksg_set_cluster(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const u
   for (uint32_t a = 0; a < c->cfg.n_anti; ++a) any_weight |= c->cfg.w_anti[a] != 0;
   for (uint32_t q = 0; q < c->cfg.n_label_pref; ++q) any_weight |= c->cfg.w_pref[q] != 0;
   d.empty_priorities = (!d.equal_fallback && !any_weight) ? 1 : 0;
-  // int64 combined scores (exact kernels) once a |score| could reach KSG_SCORE_BOUND
-  d.wide = score_bound(c->cfg, c->ext.w_taint_toleration, c->ext.w_balanced) >= (unsigned __int128)KSG_SCORE_BOUND;
   c->static_mag = 0;  // (ksg_set_static_terms' terms end with the node list they were built for)
+  // int64 combined scores (exact kernels) once a |score| could reach KSG_SCORE_BOUND, or with a
+  // capacity whose LeastRequested term leaves [0, 10]: negative, or past 2^63 / 10 (the x10 wraps)
+  c->lr_wild = c->min_cap < 0 || c->max_cap > INT64_MAX / 10;
+  set_wide(c);
   d.w_lr = c->cfg.w_least_requested;
   d.w_spread = c->cfg.w_service_spreading;
   d.n_anti = 0;
@@ -1712,8 +1757,7 @@ int ksg_set_static_terms(ksg_ctx* c, const uint64_t* fit_words, const int64_t* s
     c->static_mag += mag;
     if (score_weighted) d.empty_priorities = 0;
   }
-  d.wide = score_bound(c->cfg, c->ext.w_taint_toleration, c->ext.w_balanced) + c->static_mag >=
-           (unsigned __int128)KSG_SCORE_BOUND;
+  set_wide(c);
   return KSG_OK;
 }
 
@@ -1776,8 +1820,7 @@ int ksg_add_static_config(ksg_ctx* c, const ksg_config* extra) {
     c->static_mag += mag;
     if (weighted) d.empty_priorities = 0;
   }
-  d.wide = score_bound(c->cfg, c->ext.w_taint_toleration, c->ext.w_balanced) + c->static_mag >=
-           (unsigned __int128)KSG_SCORE_BOUND;
+  set_wide(c);
   return KSG_OK;
 }
 
@@ -1786,6 +1829,7 @@ static int add_pod_impl(ksg_ctx* c, uint32_t host_id, const ksg_pod* pod, const 
   if (int rs = cluster_ok(c)) return rs;
   int rc = check_pod(c, pod, ids, pod_ids_extent(pod));
   if (rc) return rc;
+  if (host_id < c->N && (rc = note_requests(c, pod, 1))) return rc;
   rc = mirror_add(c, host_id, pod, ids, true);
   if (rc) return rc;
   if (c->patches.size() > 4096) return flush_patches(c);
@@ -1913,6 +1957,7 @@ int ksg_schedule_begin(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, int6
   const size_t ext = call_ids_extent(c, pod);
   int rc = check_pod(c, pod, ids, ext);
   if (rc) return rc;
+  if ((rc = note_requests(c, pod, 1))) return rc;
   if (srv_eligible(c)) {  // the resident server: one request, no launch / copy / stream sync
     uint32_t hdr[KSG_SRV_HDR_DW] = {KSG_SRV_BEGIN};
     if ((rc = srv_alloc(c))) return rc;
@@ -2075,6 +2120,7 @@ int ksg_schedule_batch(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint32
   }
   hphase(0);
   int rc;
+  if ((rc = note_requests(c, pods, n))) return rc;
   if (c->dfr_neg && (rc = flush_deferred(c))) return rc;
   if ((rc = flush_patches(c))) return rc;
   if ((rc = upload_pods(c, pods, n, ids, n_ids))) return rc;
@@ -2442,8 +2488,11 @@ int ksg_schedule_batch(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint32
   }
   for (uint32_t i = 0; i < n; ++i) {
     if (out_nodes[i] < 0) continue;
+    // (this batch's commits reach the mirror, and used_hi, at the next flush_deferred)
+    c->dfr_req += (uint64_t)std::max<int64_t>(std::max(pods[i].milli_cpu, pods[i].memory), 0);
     if (pods[i].milli_cpu < 0 || pods[i].memory < 0) c->dfr_neg = true;
-    else c->dfr_sum = std::min<int64_t>(c->dfr_sum + std::min<int64_t>(pods[i].milli_cpu + pods[i].memory,
+    else c->dfr_sum = std::min<int64_t>(c->dfr_sum + std::min<int64_t>(std::min<int64_t>(pods[i].milli_cpu, KSG_WIN_LR_BOUND) +
+                                                                        std::min<int64_t>(pods[i].memory, KSG_WIN_LR_BOUND),
                                                                         KSG_WIN_LR_BOUND), KSG_WIN_LR_BOUND + 1);
   }
   hphase(7);
@@ -2470,6 +2519,7 @@ int ksg_evaluate(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, uint8_t* f
   const size_t ext = call_ids_extent(c, pod);
   int rc = check_pod(c, pod, ids, ext);
   if (rc) return rc;
+  if ((rc = note_requests(c, pod, 1))) return rc;
   if ((rc = flush_patches(c))) return rc;
   if ((rc = upload_one(c, pod, ids, ext))) return rc;
   // errors surface through the BEGIN record, so run BEGIN first for the flag
