@@ -529,6 +529,44 @@ int ksg_evaluate_ext(ksg_ctx* ctx, const ksg_pod* pod, const ksg_pod_ext* ext, c
  * (the extended-resource counterpart of ksg_read_requested). */
 int ksg_read_ext_used(ksg_ctx* ctx, int64_t* used);
 
+/* ---- FitError reports for many pods (the batch path's FailedPredicateMap) ----
+ * One device pass evaluates the predicates of n pods against every node, as
+ * ksg_evaluate does for one (generic_scheduler.go:30-44, 100-128), without scores:
+ *   codes (optional, n * n_nodes bytes): codes[i * n_nodes + node] = the KSG_FAIL_*
+ *     code of pod i on that node (0: fits). NULL: no per-node bytes are produced or
+ *     copied at all (the backlog question "which pods fit somewhere now": hist[i][0]).
+ *   hist (n * KSG_EXPLAIN_SLOTS): hist[i][c] = nodes whose code for pod i is c
+ *     (slot 0 = nodes the pod fits); a row sums to n_nodes.
+ *   err (n): 1 for a pod whose ServiceAffinity peer is on a host that is not a known
+ *     node (predicates.go:293-296; ksg_evaluate's KSG_ERR_NOPEER). Its rows of codes
+ *     and hist are zero; the other pods of the call are unaffected.
+ * ext (optional, extension contexts): ext[i] goes with pods[i]; NULL = all-zero records.
+ * The report is against the state AT THE TIME OF THE CALL: after a batch that is the
+ * state with the whole batch committed, the state a retry of the pod would meet. It
+ * equals what the sequential reference reported for pod i whenever no pod after i in
+ * the batch was placed; otherwise it may differ on the nodes that later pods took
+ * (the state "as of pod i" is not reconstructed).
+ * Every node of the cluster is covered on every rank of a sharded context (node state
+ * is replicated), with no exchange: ranks need not make the call together.
+ * uid is ignored: a pod whose uid is committed, or the same pod twice, is legal.
+ * n == 0: KSG_OK, nothing written. hist or err NULL with n > 0: KSG_ERR_ARG.
+ * KSG_ERR_STATE while a ksg_schedule_begin is pending; KSG_NONODES for an empty node
+ * list (nothing written). Pods and id extents are validated as by ksg_schedule_batch.
+ * The call changes nothing a later call can observe: not the committed totals, the
+ * generator state, the uid bookkeeping, the extended-resource usage or the results of
+ * any later batch. Unlike ksg_evaluate it does not look at the pods' requests to decide
+ * between the int32 and the int64 score kernels (it computes no score), so it leaves
+ * the path later batches take as it was. The pods are processed in chunks whose
+ * per-node codes fit a fixed device staging budget (64 MiB). */
+#define KSG_EXPLAIN_SLOTS 16   /* histogram slots per pod; codes KSG_FAIL_* 0..9 used */
+int ksg_explain_batch(ksg_ctx* ctx, const ksg_pod* pods, const ksg_pod_ext* ext /* NULL: all-zero records */,
+                      uint32_t n, const uint32_t* ids, uint32_t n_ids,
+                      uint8_t* codes /* optional, n * n_nodes */, uint32_t* hist /* n * KSG_EXPLAIN_SLOTS */,
+                      uint8_t* err /* n */);
+/* Device time (ms) of the last ksg_explain_batch's kernel launches, from HIP events
+ * on the context's stream (the copies out are not in it). Diagnostics. */
+int ksg_last_explain_ms(ksg_ctx* ctx, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

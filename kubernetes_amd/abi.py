@@ -51,6 +51,7 @@ EXT_SCALAR = 1 << 1
 FAIL_TAINTS = 8
 FAIL_SCALAR = 9
 MAX_SCALAR = 4
+EXPLAIN_SLOTS = 16  # ksg_explain_batch: histogram slots per pod (fail codes 0..9 used)
 
 MAX_ANTI = 64
 MAX_LABEL_PREF = 32
@@ -217,6 +218,8 @@ EXPORTS = [
     "ksg_schedule_batch_ext",
     "ksg_schedule_begin_ext",
     "ksg_evaluate_ext",
+    "ksg_explain_batch",
+    "ksg_last_explain_ms",
 ]
 
 # int (*ksg_allgather_fn)(void* user, const void* send, void* recv, uint64_t bytes)
@@ -287,6 +290,9 @@ def load_library() -> C.CDLL:
         "ksg_schedule_batch_ext": (C.c_int, [vp, vp, vp, U32, vp, U32, P(U64), vp]),
         "ksg_schedule_begin_ext": (C.c_int, [vp, vp, vp, vp, P(I64), P(U32), vp]),
         "ksg_evaluate_ext": (C.c_int, [vp, vp, vp, vp, vp, vp]),
+        # (ctx, pods, ext | NULL, n, ids, n_ids, codes | NULL, hist, err)
+        "ksg_explain_batch": (C.c_int, [vp, vp, vp, U32, vp, U32, vp, vp, vp]),
+        "ksg_last_explain_ms": (C.c_int, [vp, P(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

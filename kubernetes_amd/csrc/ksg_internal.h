@@ -257,6 +257,11 @@ struct KsgFused {
 typedef ksg_shard_record KsgRecordHdr;  // public layout (include/kschedgpu.h)
 // followed by nwords_max uint64 tie words (bit set = node at max_score)
 
+// ksg_explain_kernel's tiling (ksg_explain.hip): nodes per workgroup (one 64-node word per
+// wave) and pods per workgroup; grid = node tiles x pod chunks
+#define KSG_EXPLAIN_TILE 256
+#define KSG_EXPLAIN_CHUNK 32
+
 // ksg_admit_kernel modes (ksg_admit.hip)
 #define KSG_ADMIT_MODE_CAPACITY 1
 #define KSG_ADMIT_MODE_SELECTOR 2

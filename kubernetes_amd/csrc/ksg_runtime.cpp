@@ -80,6 +80,8 @@ hipError_t ksg_launch_serve(int R, bool anti, bool ext, const KsgDev& d, const K
 hipError_t ksg_launch_serve_grid(int npt, bool ext, const KsgDev& d, const KsgSrvArgs& a, hipStream_t st);
 hipError_t ksg_launch_admit(const ksg_admission_set* sets, uint32_t n_sets, const ksg_pod* pods,
                             const uint32_t* ids, const uint32_t* pairs, int mode, uint8_t* out, hipStream_t st);
+hipError_t ksg_launch_explain(const KsgDev& d, const ksg_pod* pods, const ksg_pod_ext* exts, const uint32_t* ids,
+                              uint32_t n_pods, uint8_t* codes, uint32_t* hist, uint8_t* err, hipStream_t st);
 
 namespace {
 
@@ -98,6 +100,8 @@ constexpr uint32_t kMaxNodesPerShard = KSG_R_MAX * KSG_NT;
 constexpr uint32_t kFctlGroups = 1024;
 constexpr size_t kFctlRuns = 2 * sizeof(KsgWinRun);
 constexpr size_t kFctlBytes = kFctlRuns + (size_t)2 * kFctlGroups * 8 * sizeof(uint32_t);
+// ksg_explain_batch: device staging for the per-node codes of one chunk of pods
+constexpr size_t kExplainStageBytes = (size_t)64 << 20;
 
 // Timing-only events: no system-scope fence when they complete. A default
 // hipEventRecord writes back and invalidates the caches, which costs the
@@ -183,6 +187,14 @@ struct ksg_ctx {
   uint64_t draw_tmp = 0;
   uint8_t* d_admit = nullptr;  // kubelet admission: sets, pods, ids, pairs, codes (one buffer)
   size_t admit_cap = 0;
+  // ksg_explain_batch: the per-node codes of one chunk of pods (bounded: kExplainStageBytes),
+  // the histograms uint32[n][KSG_EXPLAIN_SLOTS] then the error flags uint8[n] of the whole call
+  uint8_t* d_xcodes = nullptr;
+  size_t xcodes_cap = 0;
+  uint8_t* d_xhist = nullptr;
+  size_t xhist_cap = 0;
+  hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr;  // around its kernel launches
+  double last_explain_ms = 0.0;
   std::vector<KsgPatch> patches;
 
   // host mirror
@@ -1411,7 +1423,7 @@ int ksg_destroy(ksg_ctx* c) {
   void* scratch[] = {c->d_pods, c->d_ids, c->d_fail, c->d_score, c->d_rec_send, c->d_rec_recv, c->d_dpart,
                      c->d_dglobal, c->d_out, c->d_rng, c->d_summary, c->d_patch, c->d_shard_wlo,
                      c->d_winsum, c->d_xsend, c->d_xrecv, c->d_run, c->d_dcnt, c->d_admit, c->d_one,
-                     c->d_t0img, c->d_draws, c->d_etmax, c->d_epsoft, c->d_ethist};
+                     c->d_t0img, c->d_draws, c->d_etmax, c->d_epsoft, c->d_ethist, c->d_xcodes, c->d_xhist};
   for (void* p : scratch)
     if (p) (void)hipFree(p);
   if (c->comm) ncclCommDestroy(c->comm);
@@ -1429,6 +1441,8 @@ int ksg_destroy(ksg_ctx* c) {
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev_wait) (void)hipEventDestroy(c->ev_wait);
+  if (c->ev_x0) (void)hipEventDestroy(c->ev_x0);
+  if (c->ev_x1) (void)hipEventDestroy(c->ev_x1);
   for (auto& e : c->wev)
     if (e) (void)hipEventDestroy(e);
   if (c->st) (void)hipStreamDestroy(c->st);
@@ -2923,6 +2937,83 @@ int ksg_evaluate_ext(ksg_ctx* c, const ksg_pod* pod, const ksg_pod_ext* ext, con
   if (!rc) rc = ksg_evaluate(c, pod, ids, fail_out, score_out);
   c->cur_ext = nullptr;
   return rc;
+}
+
+// FitError reports for many pods: one grid-wide pass (ksg_explain.hip) over the device state as
+// it stands. The protocol is ksg_evaluate's (lock, no pending begin, the server leaves the stream,
+// the mirror and the patches are flushed), the validation ksg_schedule_batch's; no uid is looked
+// at and note_requests is NOT called: no score is computed, so a pod's requests need not turn the
+// context to the int64 kernels, and later batches take the path they would have taken.
+int ksg_explain_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
+                      uint32_t n_ids, uint8_t* codes, uint32_t* hist, uint8_t* err) {
+  if (!c || (n && (!pods || !hist || !err))) return KSG_ERR_ARG;
+  KSG_LOCK(c);
+  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
+  if (ext && !c->ext_on) return fail(c, KSG_ERR_STATE, "extensions are off");
+  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
+  if (int rc0 = flush_deferred(c)) return rc0;
+  if (int rs = cluster_ok(c)) return rs;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->last_explain_ms = 0.0;
+  if (n == 0) return KSG_OK;
+  if (c->N == 0) return KSG_NONODES;
+  if (n_ids && !ids) return fail(c, KSG_ERR_ARG, "ids missing");
+  int rc;
+  for (uint32_t i = 0; i < n; ++i) {
+    if ((rc = check_pod(c, pods + i, ids, n_ids))) return rc;
+    if (ext && ((rc = check_ext_range(c, ext + i, n_ids)) || (rc = check_taint_ids(c, ext + i, ids)))) return rc;
+  }
+  if ((rc = flush_patches(c))) return rc;
+  if ((rc = upload_pods(c, pods, n, ids, n_ids))) return rc;
+  const ksg_pod_ext* dext = nullptr;
+  if (ext) {  // (no record: node_fail skips the extension filters, as an all-zero record passes them)
+    if ((rc = grow(c, (void**)&c->d_pext, &c->pext_cap, n, sizeof(ksg_pod_ext)))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_pext, ext, (size_t)n * sizeof(ksg_pod_ext), hipMemcpyHostToDevice, c->st));
+    dext = c->d_pext;
+  }
+  // hist and err for the whole call; the per-node codes in a bounded staging buffer, a chunk
+  // of pods at a time (whole pod chunks of the kernel, at least one pod)
+  const size_t hb = (size_t)n * KSG_EXPLAIN_SLOTS * sizeof(uint32_t);
+  if ((rc = grow(c, (void**)&c->d_xhist, &c->xhist_cap, hb + n, 1))) return rc;
+  uint32_t* d_hist = reinterpret_cast<uint32_t*>(c->d_xhist);
+  uint8_t* d_err = c->d_xhist + hb;
+  HIPCHK(c, hipMemsetAsync(c->d_xhist, 0, hb + n, c->st));
+  uint32_t per = 1u << 20;  // pods per launch (the grid's y extent stays far below 65,535)
+  if (codes) {
+    per = (uint32_t)std::min<size_t>(per, std::max<size_t>(kExplainStageBytes / c->N, 1));
+    if (per > KSG_EXPLAIN_CHUNK) per -= per % KSG_EXPLAIN_CHUNK;
+    per = std::min(per, n);
+    if ((rc = grow(c, (void**)&c->d_xcodes, &c->xcodes_cap, (size_t)per * c->N, 1))) return rc;
+  }
+  if (!c->ev_x0) {
+    HIPCHK(c, hipEventCreate(&c->ev_x0));
+    HIPCHK(c, hipEventCreate(&c->ev_x1));
+  }
+  for (uint32_t a = 0; a < n; a += per) {
+    const uint32_t m = std::min(per, n - a);
+    HIPCHK(c, hipEventRecord(c->ev_x0, c->st));
+    HIPCHK(c, ksg_launch_explain(c->dev, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m,
+                                 codes ? c->d_xcodes : nullptr, d_hist + (size_t)a * KSG_EXPLAIN_SLOTS, d_err + a, c->st));
+    HIPCHK(c, hipEventRecord(c->ev_x1, c->st));
+    if (codes)
+      HIPCHK(c, hipMemcpyAsync(codes + (size_t)a * c->N, c->d_xcodes, (size_t)m * c->N, hipMemcpyDeviceToHost, c->st));
+    if (a + per >= n) {  // the last chunk's wait also brings hist and err back
+      HIPCHK(c, hipMemcpyAsync(hist, d_hist, hb, hipMemcpyDeviceToHost, c->st));
+      HIPCHK(c, hipMemcpyAsync(err, d_err, n, hipMemcpyDeviceToHost, c->st));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->st));  // (the staging buffer is reused by the next chunk)
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_x0, c->ev_x1));
+    c->last_explain_ms += ms;
+  }
+  return KSG_OK;
+}
+
+int ksg_last_explain_ms(ksg_ctx* c, double* ms) {
+  if (!c || !ms) return KSG_ERR_ARG;
+  KSG_LOCK(c);
+  *ms = c->last_explain_ms;
+  return KSG_OK;
 }
 
 int ksg_check_pods_exceeding_capacity(ksg_ctx* c, const ksg_admission_set* sets, uint32_t n_sets,

@@ -274,6 +274,32 @@ class DeviceScheduler:
             self._err(rc)
         return rc, fails[: hi - lo], scores[: hi - lo]
 
+    def explain(self, batch: PodBatch, want_codes: bool = True):
+        """ksg_explain_batch: the predicates of every pod of `batch` against every node of the
+        cluster as it stands, in one device pass, committing nothing.
+        -> (codes uint8[n, N] | None, hist uint32[n, EXPLAIN_SLOTS], err uint8[n]): the per-node
+        fail codes (want_codes), per pod the number of nodes with each code (slot 0: the nodes it
+        fits), and 1 where the pod's ServiceAffinity peer is on an unknown host (rows zero)."""
+        n = len(batch)
+        pods = np.ascontiguousarray(batch.pods, dtype=abi.POD_DTYPE)
+        ids = _u32(batch.ids if len(batch.ids) else np.zeros(1, np.uint32))
+        ext = None if batch.ext is None else np.ascontiguousarray(batch.ext, dtype=abi.POD_EXT_DTYPE)
+        codes = np.zeros((n, self.n_nodes), np.uint8) if want_codes else None
+        hist = np.zeros((n, abi.EXPLAIN_SLOTS), np.uint32)
+        err = np.zeros(n, np.uint8)
+        rc = self._lib.ksg_explain_batch(self._ctx, abi.ptr(pods), abi.ptr(ext), n, abi.ptr(ids), len(batch.ids),
+                                         abi.ptr(codes) if want_codes and codes.size else None, abi.ptr(hist),
+                                         abi.ptr(err))
+        if rc not in (abi.KSG_OK, abi.KSG_NONODES):
+            self._err(rc)
+        return codes, hist, err
+
+    def last_explain_ms(self) -> float:
+        """Device ms of the last explain()'s kernel launches (HIP events)."""
+        ms = C.c_double(0)
+        self._lib.ksg_last_explain_ms(self._ctx, C.byref(ms))
+        return ms.value
+
     def set_window(self, window: int):
         """Pods per speculative window (0 = exact one-pod-at-a-time kernel)."""
         rc = self._lib.ksg_set_window(self._ctx, int(window))

@@ -33,11 +33,13 @@ from .modeler import ModelerPodLister, PodMirror
 
 
 class FitError(Exception):
-    """*FitError (generic_scheduler.go:30-44)."""
+    """*FitError (generic_scheduler.go:30-44). `counts` (optional; no reference counterpart):
+    predicate name -> number of nodes it failed on, as the batch path's report gives them."""
 
-    def __init__(self, pod: Pod, failed_predicates: Dict[str, set]):
+    def __init__(self, pod: Pod, failed_predicates: Dict[str, set], counts: Optional[Dict[str, int]] = None):
         self.pod = pod
         self.failed_predicates = failed_predicates
+        self.counts = counts
         out = f"failed to find fit for pod: {pod.metadata.namespace}/{pod.metadata.name}"
         for node in sorted(failed_predicates):
             out += f"Node {node}: {','.join(sorted(failed_predicates[node]))}"
@@ -250,11 +252,18 @@ class GPUScheduler:
         return host
 
     # ---- batch path (persistent kernel) -------------------------------------
-    def schedule_batch(self, pods: Sequence[Pod], minion_lister, rng_state: int):
+    def schedule_batch(self, pods: Sequence[Pod], minion_lister, rng_state: int, explain: bool = False):
         """Schedule pods in order without host round-trips; each success is assumed
-        (committed) before the next pod. -> (hosts or None per pod, rng_state)."""
+        (committed) before the next pod. -> (hosts or None per pod, rng_state).
+        explain=True: -> (hosts, rng_state, errors), errors[i] None for a placed pod, else the
+        error Schedule would return for it: a FitError (with `counts`) built from one
+        ksg_explain_batch over the batch's unschedulable pods, or a SchedulingError for a
+        ServiceAffinity peer on an unknown host (NoMinionsError without nodes). The report is
+        against the state after the whole batch: the state a retry of the pod would meet."""
         nodes = minion_lister.list()
         if len(nodes) == 0:
+            if explain:
+                return [None] * len(pods), rng_state, [NoMinionsError() for _ in pods]
             return [None] * len(pods), rng_state
         self._sync(nodes)
         b = PodBatchBuilder(self.view, self.aff_labels)
@@ -262,7 +271,8 @@ class GPUScheduler:
         for p in pods:
             uids.append(self._uid())
             b.add(p, uids[-1])
-        out, rng_state = self.engine.batch(b.build(), rng_state)
+        batch = b.build()
+        out, rng_state = self.engine.batch(batch, rng_state)
         hosts = []
         for i, p in enumerate(pods):
             if out[i] >= 0:
@@ -273,7 +283,27 @@ class GPUScheduler:
                     self._assumed.append((p.key(), uids[i], int(out[i])))
             else:
                 hosts.append(None)
+        if explain:
+            return hosts, rng_state, self._explain(pods, batch, [i for i, h in enumerate(hosts) if h is None])
         return hosts, rng_state
+
+    def _explain(self, pods: Sequence[Pod], batch: PodBatch, idx: List[int]) -> list:
+        """errors[i] for the pods `idx` of a batch that found no node: one device pass."""
+        errors: list = [None] * len(pods)
+        if not idx:
+            return errors
+        sub = PodBatch(batch.pods[idx], batch.ids, None if batch.ext is None else batch.ext[idx])
+        codes, hist, err = self.engine.explain(sub)
+        names = self.view.names
+        for j, i in enumerate(idx):
+            if err[j]:
+                errors[i] = SchedulingError("service affinity peer is not on a known node")
+                continue
+            row = codes[j]
+            failed = {names[n]: {self.fail_names[int(row[n])]} for n in row.nonzero()[0]}
+            counts = {self.fail_names[c]: int(hist[j, c]) for c in range(1, hist.shape[1]) if hist[j, c]}
+            errors[i] = FitError(pods[i], failed, counts)
+        return errors
 
 
 def new_gpu_scheduler(config: SchedulerConfig, pod_lister, service_lister=None, random=None,
