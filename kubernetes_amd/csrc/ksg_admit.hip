@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ksg_internal.h"
+#include "ksg_launch.h"
 
 #define KSG_ADMIT_NT 64
 

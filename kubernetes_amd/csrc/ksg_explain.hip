@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ksg_device.h"
+#include "ksg_launch.h"
 
 #define KSG_EXPLAIN_WAVES (KSG_EXPLAIN_TILE / 64)
 static_assert(KSG_EXPLAIN_TILE % 64 == 0, "one bitmap word per wave");

@@ -1,0 +1,384 @@
+// ksg_host.h — what the host translation units share: the context (struct ksg_ctx), the
+// owning scratch-buffer types, the error macros, the environment switches' parsers and the
+// helpers ksg_runtime.cpp defines and ksg_batch.cpp calls.
+#ifndef KSG_HOST_H_
+#define KSG_HOST_H_
+
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+
+#include <algorithm>
+#include <array>
+#include <chrono>
+#include <cstdlib>
+#include <map>
+#include <mutex>
+#include <string>
+#include <unordered_map>
+#include <unordered_set>
+#include <vector>
+
+#include "ksg_internal.h"
+#include "ksg_launch.h"
+
+// The helpers below are shared between the host files only: they stay out of the library's
+// dynamic symbol table (the C ABI of include/kschedgpu.h is all it exports).
+#pragma GCC visibility push(hidden)
+
+int fail(ksg_ctx* c, int code, const char* fmt, ...);
+
+#define HIPCHK(c, x)                                                                 \
+  do {                                                                               \
+    hipError_t e_ = (x);                                                             \
+    if (e_ != hipSuccess)                                                            \
+      return fail((c), KSG_ERR_HIP, "%s:%d %s: %s", __FILE__, __LINE__, #x,          \
+                  hipGetErrorString(e_));                                            \
+  } while (0)
+
+#define NCCLCHK(c, x)                                                                \
+  do {                                                                               \
+    ncclResult_t r_ = (x);                                                           \
+    if (r_ != ncclSuccess)                                                           \
+      return fail((c), KSG_ERR_RCCL, "%s:%d %s: %s", __FILE__, __LINE__, #x,         \
+                  ncclGetErrorString(r_));                                           \
+  } while (0)
+
+// ---- environment switches ---------------------------------------------------
+// KSG_X=0 turns a default-on switch off, KSG_X=<non-zero> a default-off switch on
+inline bool env_flag(const char* name, bool dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) != 0 : dflt;
+}
+// the variable's integer value clamped to [lo, hi]; unset: dflt as it stands
+inline int64_t env_int(const char* name, int64_t dflt, int64_t lo, int64_t hi) {
+  const char* v = getenv(name);
+  return v ? std::min<int64_t>(std::max<int64_t>(atoll(v), lo), hi) : dflt;
+}
+
+// ---- scratch memory -----------------------------------------------------------
+// Device scratch of `cap` elements that frees itself with the context. grow() keeps the
+// contents only while the buffer is large enough: max(need, 2 x cap, 64) elements, freed
+// before the new allocation, so a warm context allocates nothing per batch.
+template <typename T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  operator T*() const { return p; }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  int grow(ksg_ctx* c, size_t need) {
+    if (need <= cap && p) return KSG_OK;
+    const size_t nc = std::max<size_t>(need, std::max<size_t>(cap * 2, 64));
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    HIPCHK(c, hipMalloc((void**)&p, nc * sizeof(T)));
+    cap = nc;
+    return KSG_OK;
+  }
+};
+
+// Pinned host staging of `cap` bytes: max(need, 2 x cap, 4096) (geometric: a pinned
+// (re)allocation costs ~0.2 ms, hipHostFree synchronises)
+struct HostBuf {
+  uint8_t* p = nullptr;
+  size_t cap = 0;
+  HostBuf() = default;
+  HostBuf(const HostBuf&) = delete;
+  HostBuf& operator=(const HostBuf&) = delete;
+  ~HostBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+  operator uint8_t*() const { return p; }
+  int grow(ksg_ctx* c, size_t need) {
+    if (cap >= need) return KSG_OK;
+    const size_t nc = std::max<size_t>(need, std::max<size_t>(cap * 2, 4096));
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+    HIPCHK(c, hipHostMalloc((void**)&p, nc, hipHostMallocDefault));
+    cap = nc;
+    return KSG_OK;
+  }
+};
+
+struct PodRec {
+  uint32_t host;
+  int64_t cpu, mem;
+  int64_t scalar[KSG_MAX_SCALAR];  // extension: extended resource requests
+  std::vector<uint32_t> keys;  // ports + PDs
+  std::vector<uint32_t> svcs;
+  uint64_t seq;
+};
+
+// the fused window launch's control block: two KsgWinRun slots, then the pod groups'
+// counters uint32[2][kFctlGroups][8] (a window of up to 4 x kFctlGroups pods)
+constexpr uint32_t kFctlGroups = 1024;
+constexpr size_t kFctlRuns = 2 * sizeof(KsgWinRun);
+constexpr size_t kFctlBytes = kFctlRuns + (size_t)2 * kFctlGroups * 8 * sizeof(uint32_t);
+
+// Timing-only events: no system-scope fence when they complete. A default
+// hipEventRecord writes back and invalidates the caches, which costs the
+// stream time between the window kernels and evicts the node state the next
+// kernel reads from L2 (KSG_EVENT_FENCE=1 restores the default for A/B).
+inline const unsigned kTimingEvent = env_flag("KSG_EVENT_FENCE", false) ? hipEventDefault : hipEventDisableSystemFence;
+
+#pragma GCC visibility pop
+
+struct ksg_ctx {
+  ksg_config cfg{};
+  int device = 0, rank = 0, world = 1;
+  hipStream_t st = nullptr;
+  ncclComm_t comm = nullptr;
+  bool xchg = false;  // exchange path: world > 1, or a 1-rank RCCL communicator
+  double ppw_est = 0.0;  // pods resolved per window (window path round sizing)
+  // windows per round = margin x (pods left) / ppw_est + 1 (KSG_ROUND_MARGIN): the
+  // launches past the batch's end cost ~8 us each, a second round a host round trip
+  double round_margin = 1.0;
+  // pinned staging for the per-call uploads / small read-backs (a pageable
+  // hipMemcpyAsync is a staged, effectively synchronous copy)
+  HostBuf h_up, h_dn;
+  // host-staged exchange (ksg_set_allgather) for sharded contexts without RCCL
+  ksg_allgather_fn xfn = nullptr;
+  void* xuser = nullptr;
+  HostBuf h_xsend, h_xrecv;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  // the batch path's waits spin on this event (KSG_SPIN_WAIT=0: hipStreamSynchronize)
+  hipEvent_t ev_wait = nullptr;
+  bool spin_wait = true;
+  double last_ms = 0.0;
+  std::string err;
+
+  // cluster
+  bool have_cluster = false;
+  // a batch failed after its device work was enqueued: the device may hold some
+  // of its commits and the host mirror none, so every call fails until
+  // ksg_set_cluster uploads the cluster again
+  bool diverged = false;
+  uint32_t N = 0, nw = 0, n_pairs = 0, S = 0, D = 0;
+  uint32_t lo = 0, hi = 0, wlo = 0, nwords = 0, nwords_max = 0;
+  std::vector<uint32_t> shard_wlo_h;
+  int R = 1;
+  size_t lds = 0;
+  KsgDev dev{};
+  std::vector<void*> cluster_allocs;
+  DevBuf<uint32_t> d_shard_wlo;
+  DevBuf<int32_t> dbgbuf;  // dev.dbgbuf's owner (KSG_DEBUG & (8 | 32 | 64))
+
+  // scratch
+  DevBuf<ksg_pod> d_pods;
+  DevBuf<uint32_t> d_ids;
+  DevBuf<uint8_t> d_fail;
+  DevBuf<int64_t> d_score;
+  DevBuf<uint8_t> d_rec_send, d_rec_recv;
+  uint32_t rec_bytes = 0;
+  DevBuf<int32_t> d_dpart, d_dglobal;
+  DevBuf<int32_t> d_out;
+  DevBuf<uint64_t> d_rng;
+  DevBuf<int64_t> d_summary;
+  // the per-pod path (begin / commit / evaluate): the pod and its id list in
+  // one device buffer (one copy in), and the decide kernel's summary and chosen
+  // node written straight into pinned host memory (no copy out)
+  DevBuf<uint8_t> d_one;
+  const ksg_pod* one_pod = nullptr;
+  const uint32_t* one_ids = nullptr;
+  uint8_t* h_map = nullptr;  // pinned, coherent: [0, 32) summary int64[3], [32, 36) node
+  uint8_t* d_map = nullptr;  // its device address
+  DevBuf<KsgPatch> d_patch;
+  DevBuf<uint64_t> d_draws;  // ksg_schedule_batch_draws: the caller's rand.Int() values
+  uint64_t draw_tmp = 0;
+  DevBuf<uint8_t> d_admit;  // kubelet admission: sets, pods, ids, pairs, codes (one buffer)
+  // ksg_explain_batch: the per-node codes of one chunk of pods (bounded: kExplainStageBytes),
+  // the histograms uint32[n][KSG_EXPLAIN_SLOTS] then the error flags uint8[n] of the whole call
+  DevBuf<uint8_t> d_xcodes, d_xhist;
+  hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr;  // around its kernel launches
+  double last_explain_ms = 0.0;
+  std::vector<KsgPatch> patches;
+
+  // host mirror
+  std::vector<int64_t> used_c, used_m;
+  // max over nodes of used_c / used_m for use_window: raised by each mirror add,
+  // recomputed after anything else changes them (a removal, a negative total)
+  int64_t mu_max = 0;
+  bool mu_neg = false, mu_dirty = true;
+  std::unordered_map<uint64_t, uint32_t> key_ref;  // (key << 32) | node
+  std::vector<int32_t> svc_cnt;                    // S*N
+  std::vector<std::unordered_map<uint32_t, int32_t>> svc_ext;
+  std::vector<int32_t> svc_max, svc_total, svc_peer;
+  std::vector<int32_t> h_aff_pair;  // [affinity label][node] (ServiceAffinity, one rank; ksg_set_cluster)
+  std::vector<std::map<uint64_t, uint32_t>> svc_members;  // seq -> host
+  std::unordered_map<uint64_t, PodRec> pods;
+  uint64_t seq = 0;
+
+  // window (speculative) path
+  uint32_t window = 128;        // 0 = exact one-pod-at-a-time kernel
+  // HIP events around every ev_stride-th window launch (phase A and resolver;
+  // KSG_KERNEL_EVENTS=N: every N-th, 0: none). An event between two dependent
+  // launches lengthens the gap between them, so a sample of the windows is timed
+  // and the per-launch mean scaled to all launches (ksg_last_batch_kernel_ms).
+  uint32_t ev_stride = 4;
+  uint32_t ev_phase = 0;  // which launches of a round are timed; advances every round
+  DevBuf<KsgWinSum> d_winsum;
+  DevBuf<uint8_t> d_xsend;   // phase A block of this shard (KsgWinXchg layout)
+  DevBuf<uint8_t> d_xrecv;   // all-gathered blocks of every shard (world > 1)
+  DevBuf<uint8_t> d_t0img;   // the plain resolver's T0 images, one per window pod
+  DevBuf<int32_t> d_dcnt;    // [W][D] per-pod anti-affinity domain counts (phase A pre-pass)
+  DevBuf<int32_t> d_dmb;     // [W][D+1] re-rank: best score without the anti term per domain row
+  uint64_t* d_zmap = nullptr;  // [D+1][nw] re-rank: nodes of each domain row (cluster allocation)
+  DevBuf<int32_t> d_etmax;    // [W] extension scores: TaintToleration max per window pod (count pass)
+  DevBuf<int32_t> d_ethist;   // [W][KSG_TBINS] ... the histogram of its soft-taint counts
+  DevBuf<uint64_t> d_epsoft;  // [W] ... the pods' untolerated soft taints as masks
+  DevBuf<KsgWinRun> d_run;         // progress of the window chain (device)
+  KsgWinRun* h_run = nullptr;      // pinned host copy
+  uint32_t last_stats[4] = {0, 0, 0, 0};  // windows, stops (service scalar), stops (ties exhausted)
+  std::vector<hipEvent_t> wev;     // event pairs around the chained window kernels
+  double last_kms[3] = {0, 0, 0};  // phase A ms, phase B ms, launches (window path)
+  double last_t0ms = 0;            // ... and between them: the exchange (sharded) and the T0 images
+  double last_wsum = 0;            // window capacity W summed over the launches
+  bool dbg_fail_next = false;      // KSG_DEBUG & 16384: the next window batch fails after its device work
+  uint32_t dbg_corrupt = 0;        // KSG_DEBUG bits 22 / 23: corrupt the next COMMIT / BEGIN request's layout
+  bool win_d1 = true;              // phase A's single-commit drop bitmaps (KSG_WIN_D1=0: off; ksg_plain.hip)
+  // the fused window launch (KsgFused, ksg_plain.hip): one launch per window on one rank without
+  // ServiceAntiAffinity or extensions (KSG_FUSED=0: phase A, T0 images and resolver apart)
+  bool win_fused = true;
+  uint32_t fused_grid = 0;          // its blocks: one per CU (KSG_FUSED_GRID overrides)
+  // ... up to this many 64-node words per shard (KSG_FUSED_MAX_WORDS; 65,536 nodes): past them the
+  // scoring blocks, one per CU under the resolver's LDS, are too few waves to hide phase A's load
+  // latency (config 5, 100k nodes, same box: 255k fused against 385k apart; 45k nodes: 492k fused
+  // against 465k, profiles/r6_fused_threshold.json)
+  uint32_t fused_max_words = 1024;
+  uint8_t* d_fctl = nullptr;        // KsgWinRun[2], then the counters uint32[2][groups][8]
+  uint8_t* h_fctl = nullptr;        // pinned: the round's first slot and zeroed counters
+  double last_hus[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // host us per phase of the last batch (ksg_last_batch_host_us)
+  double totals[24] = {};  // ksg_batch_totals: the per-batch diagnostics summed over batches
+  int64_t max_cap = 0, min_cap = 0;
+
+  // Commits of the last ksg_schedule_batch not yet replayed into the host
+  // mirror: replayed while the next batch runs on the device, or before any
+  // call that reads the mirror (flush_deferred).
+  std::vector<ksg_pod> dfr_pods;
+  std::vector<uint32_t> dfr_ids;
+  std::vector<int32_t> dfr_out;
+  std::unordered_set<uint64_t> dfr_uids;
+  int64_t dfr_sum = 0;   // sum of the deferred pods' requests (cpu + memory), capped
+  bool dfr_neg = false;  // a deferred pod has a negative request
+  // calculateScore (priorities.go:27-37) stays in [0, 10] only while capacities lie in
+  // [0, 2^63 / 10] and requested totals are non-negative; score_bound() assumes that range.
+  // lr_wild: this node list, or a pod seen since ksg_set_cluster, can take a LeastRequested
+  // term out of it (a negative capacity or one whose x10 wraps, a negative request, a total
+  // that wraps): the int64 score kernels serve the context from then on (KsgDev.wide)
+  bool lr_wild = false;
+  int64_t used_hi = 0;                // the largest committed total the mirror has held
+  unsigned __int128 dfr_req = 0;      // requests of batches whose commits are not in the mirror yet
+
+  // extensions (ksg_set_extensions; exact kernels, one rank, parity unpinned)
+  bool ext_on = false;
+  ksg_ext_config ext{};
+  std::vector<int64_t> sc_used;  // [n_scalar][N] host mirror of scalar_used
+  std::unordered_map<uint64_t, std::array<int64_t, KSG_MAX_SCALAR>> ext_scalar;  // uid -> requests
+  const ksg_pod_ext* cur_ext = nullptr;  // the _ext entry point's records for this call
+  DevBuf<ksg_pod_ext> d_pext;            // device copy (batch / explain)
+  ksg_pod_ext* d_one_ext = nullptr;      // the single pod's record (inside d_one)
+
+  // the resident drop-in server (ksg_serve.hip): begin / commit as requests in
+  // mapped host memory instead of launches, copies and stream syncs
+  bool srv_enabled = true;      // KSG_SERVE=0: the launch-per-call path
+  bool srv_running = false;     // a server kernel may be resident on `st`
+  KsgSrvBox* srv_box = nullptr;   // pinned, coherent, mapped
+  KsgSrvBox* srv_dbox = nullptr;  // its device address
+  uint8_t* srv_fail = nullptr;    // fail codes of the shard's nodes (mapped)
+  uint8_t* srv_dfail = nullptr;
+  size_t srv_fail_cap = 0;
+  uint32_t srv_seq = 0;         // last request posted
+  uint64_t srv_idle_us = 20000; // the server returns after this long without a request
+  bool pend_srv = false;        // the pending begin was served by the server
+  uint32_t srv_bhdr[KSG_SRV_HDR_DW] = {};  // that begin's header (its payload layout)
+  std::vector<uint64_t> srv_tw;  // its tie words (node lo + 64 i + b), the commit picks from them
+  uint32_t srv_unacked = 0;      // a COMMIT posted without waiting for its answer (0: none)
+  uint32_t srv_served = 0;       // every request up to this one was served
+  uint32_t srv_last_ctl = 0;     // the last control request posted
+  bool srv_pext_on = false;      // the pending begin's extension record (its commit carries it)
+  ksg_pod_ext srv_pext{};
+  uint64_t srv_launches = 0;
+  bool srv_grid_on = true;       // KSG_SERVE_GRID=0: the one-workgroup server at every size
+  uint32_t srv_npt4_min = 16384;  // KSG_SERVE_GRID_NPT4_MIN: past this many nodes 4 nodes per thread
+  // KSG_SERVE_GRID_MIN: shards above this many nodes take the grid server
+  // (it beats the one-workgroup server at 500 nodes already: 7.2 vs 10.9 us)
+  uint32_t srv_grid_min = 0;
+  bool srv_grid_ext = true;  // KSG_SERVE_GRID_EXT=0: extension contexts on the one-workgroup server
+  KsgSrvGrid* srv_grid = nullptr;  // its device state (+ the fail codes)
+  size_t srv_grid_cap = 0;
+  uint32_t srv_epoch = 0;
+  bool srv_stamps = false;      // KSG_SERVE_STAMPS=1: sum the server's per-stage cycles of each begin
+  int64_t srv_grid_opts = -1;   // KSG_SERVE_GRID_OPTS (KsgSrvArgs.grid_opts; -1: by size)
+  bool srv_debug = false;       // KSG_SERVE_DEBUG=1: the grid server's stage markers, reported on a fault
+  unsigned __int128 static_mag = 0;  // max |score| of the terms ksg_set_static_terms added
+  // the node labels on the device (ksg_add_static_config evaluates more static terms from them)
+  const ksg_node* d_lbl_nodes = nullptr;
+  const uint32_t* d_lbl_pairs = nullptr;
+  const uint32_t* d_lbl_keys = nullptr;
+  bool srv_trace = false;       // KSG_SERVE_TRACE=1: every post, wait and relaunch to stderr
+  double srv_stage[6] = {};     // (printed by ksg_destroy)
+  uint64_t srv_stamped = 0;
+
+  // begin/commit
+  bool pending = false;
+  uint64_t pending_k = 0;
+  ksg_pod pend{};
+  std::vector<uint32_t> pend_ids;
+
+  // Every entry point holds `mu`, so reflector threads may call ksg_add_pod /
+  // ksg_remove_pod while the scheduling thread schedules. Updates that arrive
+  // between ksg_schedule_begin and its commit are queued (validated first) and
+  // applied, in arrival order, when the pending pod is committed or abandoned:
+  // between pods, never inside one (SURVEY.md 8(b) "Threading").
+  std::recursive_mutex mu;
+  struct Queued {
+    bool add;
+    uint32_t host;
+    ksg_pod pod;
+    std::vector<uint32_t> ids;
+    uint64_t uid;
+  };
+  std::vector<Queued> upd_q;
+  std::unordered_set<uint64_t> q_added, q_removed;
+};
+
+#define KSG_LOCK(c) std::lock_guard<std::recursive_mutex> ksg_lock_((c)->mu)
+
+// ---- ksg_runtime.cpp's helpers the batch driver (ksg_batch.cpp) calls -----------
+#pragma GCC visibility push(hidden)
+
+enum class Reduce { Sum, Max };
+
+int check_pod(ksg_ctx* c, const ksg_pod* p, const uint32_t* ids, size_t n_ids);
+int note_requests(ksg_ctx* c, const ksg_pod* pods, uint32_t n);
+int flush_deferred(ksg_ctx* c);
+void drop_deferred(ksg_ctx* c);
+int flush_patches(ksg_ctx* c);
+int upload_pods(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint32_t* ids, size_t n_ids);
+int wait_device(ksg_ctx* c);
+int cluster_ok(ksg_ctx* c);
+int srv_stop(ksg_ctx* c);
+int scan_exchange(ksg_ctx* c, const ksg_pod* dpod, const uint32_t* dids, int mode, uint8_t* fail_out,
+                  int64_t* score_out, const ksg_pod_ext* dext);
+int allgather(ksg_ctx* c, const void* dsend, void* drecv, size_t bytes);
+int allreduce_i32(ksg_ctx* c, Reduce op, const int32_t* dsend, int32_t* drecv, uint32_t n);
+bool anti_on(const ksg_ctx* c);
+uint8_t* rec_buf(ksg_ctx* c);
+extern "C" {  // (defined among the entry points, inside ksg_runtime.cpp's extern "C" block)
+int remove_pod_impl(ksg_ctx* c, uint64_t uid);
+int note_ext(ksg_ctx* c, const ksg_pod* p, const ksg_pod_ext* e, size_t n_ids);
+int check_ext_range(ksg_ctx* c, const ksg_pod_ext* e, size_t n_ids);
+int check_taint_ids(ksg_ctx* c, const ksg_pod_ext* e, const uint32_t* ids);
+}
+
+#pragma GCC visibility pop
+
+#endif  // KSG_HOST_H_

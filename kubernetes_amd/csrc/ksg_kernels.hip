@@ -24,6 +24,7 @@
 
 #include "ksg_device.h"
 #include "ksg_exact.h"
+#include "ksg_launch.h"
 #include "ksg_shard.h"
 
 // ============================================================================

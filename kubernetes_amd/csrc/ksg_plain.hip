@@ -85,6 +85,7 @@
 // counts). The committer reads an entry only for its own pod. Every
 // wait has a spin limit; a timed-out wait sets ctl->hang and the host fails
 // the batch.
+#include "ksg_launch.h"
 #include "ksg_resolver.h"
 #include "ksg_score.h"
 

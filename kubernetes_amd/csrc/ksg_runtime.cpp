@@ -1,7 +1,11 @@
 // ksg_runtime.cpp — host runtime of libkschedgpu.so: the C ABI in
-// include/kschedgpu.h, the device-state mirror, and the RCCL exchange.
+// include/kschedgpu.h except the batch entry points, the device-state mirror, the
+// RCCL exchange, the per-pod path (begin / commit / evaluate) with its resident
+// server, kubelet admission, the extensions and ksg_explain_batch. The batch driver
+// (ksg_schedule_batch and its variants) is ksg_batch.cpp; ksg_host.h holds what the
+// two files share (struct ksg_ctx, the scratch-buffer types, the helpers declared there).
 //
-// Reference behaviour mirrored here (under /root/reference):
+// Reference behaviour mirrored here:
 //   genericScheduler.Schedule / selectHost     pkg/scheduler/generic_scheduler.go:54-96
 //   MapPodsToMachines (pods keyed by Status.Host)  pkg/scheduler/predicates.go:354-375
 //   SimpleModeler.AssumePod / listPods        plugin/pkg/scheduler/modeler.go:77-139
@@ -12,347 +16,14 @@
 // ksg_remove_pod can undo exactly; the device copy is authoritative for
 // scheduling and is patched from the mirror. All scheduling decisions run in
 // the HIP kernels (ksg_kernels.hip); there is no CPU evaluation path.
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
-#include <algorithm>
-#include <array>
 #include <atomic>
-#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <map>
-#include <mutex>
-#include <string>
-#include <unordered_map>
-#include <unordered_set>
-#include <vector>
 
-#include "ksg_internal.h"
+#include "ksg_host.h"
 #include "ksg_shard.h"
-
-
-hipError_t ksg_launch_batch(int R, bool anti, const KsgDev& d, const ksg_pod* pods,
-                            const uint32_t* ids, uint32_t n, uint64_t* rng, int32_t* out,
-                            hipStream_t st, const ksg_pod_ext* ext = nullptr);
-hipError_t ksg_launch_scan(int R, bool anti, const KsgDev& d, const ksg_pod* pods,
-                           const uint32_t* ids, int mode, int phase, uint8_t* fail_out,
-                           int64_t* score_out, uint8_t* record, int32_t* dpart,
-                           const int32_t* dglobal, hipStream_t st, const ksg_pod_ext* ext = nullptr);
-hipError_t ksg_launch_win_eval(const KsgDev& d, int mode, const ksg_pod* batch, const uint32_t* ids,
-                               const KsgWinRun* run, uint32_t wcap, KsgWinSum* sums, uint64_t* wbits, int32_t* wmax,
-                               uint32_t ostride, int32_t* dcnt, uint64_t* wfit, int32_t* dmb, uint64_t* wbz,
-                               uint32_t dz, hipStream_t st, const ksg_pod_ext* exts = nullptr,
-                               int32_t* tmax = nullptr, uint64_t* psoft = nullptr, int32_t* thist = nullptr);
-hipError_t ksg_launch_zonemap(uint32_t n_nodes, const int32_t* anti_domain, uint32_t d0, uint32_t nw,
-                              uint64_t* zmap, hipStream_t st);
-hipError_t ksg_launch_win_t0(const KsgDev& d, uint32_t wcap, const KsgWinRun* run, const KsgWinXchg& x,
-                             hipStream_t st);
-uint32_t ksg_win_t0_stride(const KsgDev& d);
-hipError_t ksg_launch_win_resolve(const KsgDev& d, uint32_t wcap, KsgWinRun* run, const KsgWinSum* sums,
-                                  const KsgWinXchg& x, uint64_t* rng, int32_t* out, hipStream_t st);
-bool ksg_win_fused_ok(const KsgDev& d);
-uint32_t ksg_win_fused_groups(const KsgDev& d, uint32_t wcap);
-hipError_t ksg_launch_win_fused(const KsgDev& d, uint32_t wcap, KsgWinRun* run, const KsgWinSum* sums,
-                                const KsgWinXchg& x, uint64_t* rng, int32_t* out, const KsgFused& f, uint32_t grid,
-                                hipStream_t st);
-uint32_t ksg_win_max_window(const KsgDev& d);
-hipError_t ksg_launch_decide(const KsgDev& d, const ksg_pod* pods, const uint32_t* ids,
-                             const uint8_t* records, uint32_t rec_bytes, uint32_t world,
-                             const uint32_t* shard_wlo, int mode, uint64_t tie_index,
-                             uint64_t* rng, int32_t* out, uint32_t out_idx, int64_t* summary,
-                             hipStream_t st, const ksg_pod_ext* ext = nullptr);
-hipError_t ksg_launch_static(const KsgStaticCfg& sc, uint32_t n_nodes, const ksg_node* nodes,
-                             const uint32_t* node_pairs, const uint32_t* pair_keys,
-                             const int32_t* dom_of_pair, uint32_t n_pairs, uint32_t nw,
-                             uint64_t* static_fit, int64_t* static_score, int32_t* anti_domain,
-                             int32_t* aff_pair, unsigned long long* pairmap, hipStream_t st);
-hipError_t ksg_launch_patch(const KsgPatch* patches, uint32_t n, hipStream_t st);
-hipError_t ksg_launch_static_terms(const KsgStaticCfg& sc, uint32_t n_nodes, const ksg_node* nodes,
-                                   const uint32_t* node_pairs, const uint32_t* pair_keys, uint32_t n_pairs, uint32_t nw,
-                                   uint64_t* fit, int64_t* score, hipStream_t st);
-hipError_t ksg_launch_static_fold(uint64_t* static_fit, int64_t* static_score, const uint64_t* xfit,
-                                  const int64_t* xscore, uint32_t nw, uint32_t n, int own_fit, int own_score,
-                                  hipStream_t st);
-hipError_t ksg_launch_serve(int R, bool anti, bool ext, const KsgDev& d, const KsgSrvArgs& a, hipStream_t st);
-hipError_t ksg_launch_serve_grid(int npt, bool ext, const KsgDev& d, const KsgSrvArgs& a, hipStream_t st);
-hipError_t ksg_launch_admit(const ksg_admission_set* sets, uint32_t n_sets, const ksg_pod* pods,
-                            const uint32_t* ids, const uint32_t* pairs, int mode, uint8_t* out, hipStream_t st);
-hipError_t ksg_launch_explain(const KsgDev& d, const ksg_pod* pods, const ksg_pod_ext* exts, const uint32_t* ids,
-                              uint32_t n_pods, uint8_t* codes, uint32_t* hist, uint8_t* err, hipStream_t st);
-
-namespace {
-
-struct PodRec {
-  uint32_t host;
-  int64_t cpu, mem;
-  int64_t scalar[KSG_MAX_SCALAR];  // extension: extended resource requests
-  std::vector<uint32_t> keys;  // ports + PDs
-  std::vector<uint32_t> svcs;
-  uint64_t seq;
-};
-
-constexpr uint32_t kMaxNodesPerShard = KSG_R_MAX * KSG_NT;
-// the fused window launch's control block: two KsgWinRun slots, then the pod groups'
-// counters uint32[2][kFctlGroups][8] (a window of up to 4 x kFctlGroups pods)
-constexpr uint32_t kFctlGroups = 1024;
-constexpr size_t kFctlRuns = 2 * sizeof(KsgWinRun);
-constexpr size_t kFctlBytes = kFctlRuns + (size_t)2 * kFctlGroups * 8 * sizeof(uint32_t);
-// ksg_explain_batch: device staging for the per-node codes of one chunk of pods
-constexpr size_t kExplainStageBytes = (size_t)64 << 20;
-
-// Timing-only events: no system-scope fence when they complete. A default
-// hipEventRecord writes back and invalidates the caches, which costs the
-// stream time between the window kernels and evicts the node state the next
-// kernel reads from L2 (KSG_EVENT_FENCE=1 restores the default for A/B).
-const unsigned kTimingEvent =
-    (getenv("KSG_EVENT_FENCE") && atoi(getenv("KSG_EVENT_FENCE"))) ? hipEventDefault : hipEventDisableSystemFence;
-
-}  // namespace
-
-struct ksg_ctx {
-  ksg_config cfg{};
-  int device = 0, rank = 0, world = 1;
-  hipStream_t st = nullptr;
-  ncclComm_t comm = nullptr;
-  bool xchg = false;
-  double ppw_est = 0.0;  // pods resolved per window (window path round sizing)
-  // windows per round = margin x (pods left) / ppw_est + 1 (KSG_ROUND_MARGIN): the
-  // launches past the batch's end cost ~8 us each, a second round a host round trip
-  double round_margin = 1.0;
-  // pinned staging for the per-call uploads / small read-backs (a pageable
-  // hipMemcpyAsync is a staged, effectively synchronous copy)
-  uint8_t* h_up = nullptr;
-  size_t h_up_cap = 0;
-  uint8_t* h_dn = nullptr;
-  size_t h_dn_cap = 0;  // exchange path: world > 1, or a 1-rank RCCL communicator
-  // host-staged exchange (ksg_set_allgather) for sharded contexts without RCCL
-  ksg_allgather_fn xfn = nullptr;
-  void* xuser = nullptr;
-  uint8_t *h_xsend = nullptr, *h_xrecv = nullptr;
-  size_t h_xsend_cap = 0, h_xrecv_cap = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // the batch path's waits spin on this event (KSG_SPIN_WAIT=0: hipStreamSynchronize)
-  hipEvent_t ev_wait = nullptr;
-  bool spin_wait = true;
-  double last_ms = 0.0;
-  std::string err;
-
-  // cluster
-  bool have_cluster = false;
-  // a batch failed after its device work was enqueued: the device may hold some
-  // of its commits and the host mirror none, so every call fails until
-  // ksg_set_cluster uploads the cluster again
-  bool diverged = false;
-  uint32_t N = 0, nw = 0, n_pairs = 0, S = 0, D = 0;
-  uint32_t lo = 0, hi = 0, wlo = 0, nwords = 0, nwords_max = 0;
-  std::vector<uint32_t> shard_wlo_h;
-  int R = 1;
-  size_t lds = 0;
-  KsgDev dev{};
-  std::vector<void*> cluster_allocs;
-  uint32_t* d_shard_wlo = nullptr;
-
-  // scratch
-  ksg_pod* d_pods = nullptr;
-  size_t pods_cap = 0;
-  uint32_t* d_ids = nullptr;
-  size_t ids_cap = 0;
-  uint8_t* d_fail = nullptr;
-  int64_t* d_score = nullptr;
-  uint8_t* d_rec_send = nullptr;
-  uint8_t* d_rec_recv = nullptr;
-  uint32_t rec_bytes = 0;
-  int32_t* d_dpart = nullptr;
-  int32_t* d_dglobal = nullptr;
-  int32_t* d_out = nullptr;
-  size_t out_cap = 0;
-  uint64_t* d_rng = nullptr;
-  int64_t* d_summary = nullptr;
-  // the per-pod path (begin / commit / evaluate): the pod and its id list in
-  // one device buffer (one copy in), and the decide kernel's summary and chosen
-  // node written straight into pinned host memory (no copy out)
-  uint8_t* d_one = nullptr;
-  size_t one_cap = 0;
-  const ksg_pod* one_pod = nullptr;
-  const uint32_t* one_ids = nullptr;
-  uint8_t* h_map = nullptr;  // pinned, coherent: [0, 32) summary int64[3], [32, 36) node
-  uint8_t* d_map = nullptr;  // its device address
-  KsgPatch* d_patch = nullptr;
-  size_t patch_cap = 0;
-  uint64_t* d_draws = nullptr;  // ksg_schedule_batch_draws: the caller's rand.Int() values
-  size_t draws_cap = 0;
-  uint64_t draw_tmp = 0;
-  uint8_t* d_admit = nullptr;  // kubelet admission: sets, pods, ids, pairs, codes (one buffer)
-  size_t admit_cap = 0;
-  // ksg_explain_batch: the per-node codes of one chunk of pods (bounded: kExplainStageBytes),
-  // the histograms uint32[n][KSG_EXPLAIN_SLOTS] then the error flags uint8[n] of the whole call
-  uint8_t* d_xcodes = nullptr;
-  size_t xcodes_cap = 0;
-  uint8_t* d_xhist = nullptr;
-  size_t xhist_cap = 0;
-  hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr;  // around its kernel launches
-  double last_explain_ms = 0.0;
-  std::vector<KsgPatch> patches;
-
-  // host mirror
-  std::vector<int64_t> used_c, used_m;
-  // max over nodes of used_c / used_m for use_window: raised by each mirror add,
-  // recomputed after anything else changes them (a removal, a negative total)
-  int64_t mu_max = 0;
-  bool mu_neg = false, mu_dirty = true;
-  std::unordered_map<uint64_t, uint32_t> key_ref;  // (key << 32) | node
-  std::vector<int32_t> svc_cnt;                    // S*N
-  std::vector<std::unordered_map<uint32_t, int32_t>> svc_ext;
-  std::vector<int32_t> svc_max, svc_total, svc_peer;
-  std::vector<int32_t> h_aff_pair;  // [affinity label][node] (ServiceAffinity, one rank; ksg_set_cluster)
-  std::vector<std::map<uint64_t, uint32_t>> svc_members;  // seq -> host
-  std::unordered_map<uint64_t, PodRec> pods;
-  uint64_t seq = 0;
-
-  // window (speculative) path
-  uint32_t window = 128;        // 0 = exact one-pod-at-a-time kernel
-  // HIP events around every ev_stride-th window launch (phase A and resolver;
-  // KSG_KERNEL_EVENTS=N: every N-th, 0: none). An event between two dependent
-  // launches lengthens the gap between them, so a sample of the windows is timed
-  // and the per-launch mean scaled to all launches (ksg_last_batch_kernel_ms).
-  uint32_t ev_stride = 4;
-  uint32_t ev_phase = 0;  // which launches of a round are timed; advances every round
-  KsgWinSum* d_winsum = nullptr;
-  uint8_t* d_xsend = nullptr;   // phase A block of this shard (KsgWinXchg layout)
-  uint8_t* d_xrecv = nullptr;   // all-gathered blocks of every shard (world > 1)
-  uint8_t* d_t0img = nullptr;   // the plain resolver's T0 images, one per window pod
-  size_t t0img_cap = 0;
-  int32_t* d_dcnt = nullptr;     // [W][D] per-pod anti-affinity domain counts (phase A pre-pass)
-  int32_t* d_dmb = nullptr;      // [W][D+1] re-rank: best score without the anti term per domain row
-  uint64_t* d_zmap = nullptr;    // [D+1][nw] re-rank: nodes of each domain row (cluster allocation)
-  size_t win_cap = 0, xsend_cap = 0, xrecv_cap = 0, dcnt_cap = 0, dmb_cap = 0;
-  int32_t* d_etmax = nullptr;    // [W] extension scores: TaintToleration max per window pod (count pass)
-  int32_t* d_ethist = nullptr;   // [W][KSG_TBINS] ... the histogram of its soft-taint counts
-  size_t ethist_cap = 0;
-  uint64_t* d_epsoft = nullptr;  // [W] ... the pods' untolerated soft taints as masks
-  size_t etmax_cap = 0, epsoft_cap = 0;
-  KsgWinRun* d_run = nullptr;      // progress of the window chain (device)
-  KsgWinRun* h_run = nullptr;      // pinned host copy
-  uint32_t last_stats[4] = {0, 0, 0, 0};  // windows, stops (service scalar), stops (ties exhausted)
-  std::vector<hipEvent_t> wev;     // event pairs around the chained window kernels
-  double last_kms[3] = {0, 0, 0};  // phase A ms, phase B ms, launches (window path)
-  double last_t0ms = 0;            // ... and between them: the exchange (sharded) and the T0 images
-  double last_wsum = 0;            // window capacity W summed over the launches
-  bool dbg_fail_next = false;      // KSG_DEBUG & 16384: the next window batch fails after its device work
-  uint32_t dbg_corrupt = 0;        // KSG_DEBUG bits 22 / 23: corrupt the next COMMIT / BEGIN request's layout
-  bool win_d1 = true;              // phase A's single-commit drop bitmaps (KSG_WIN_D1=0: off; ksg_plain.hip)
-  // the fused window launch (KsgFused, ksg_plain.hip): one launch per window on one rank without
-  // ServiceAntiAffinity or extensions (KSG_FUSED=0: phase A, T0 images and resolver apart)
-  bool win_fused = true;
-  uint32_t fused_grid = 0;          // its blocks: one per CU (KSG_FUSED_GRID overrides)
-  // ... up to this many 64-node words per shard (KSG_FUSED_MAX_WORDS; 65,536 nodes): past them the
-  // scoring blocks, one per CU under the resolver's LDS, are too few waves to hide phase A's load
-  // latency (config 5, 100k nodes, same box: 255k fused against 385k apart; 45k nodes: 492k fused
-  // against 465k, profiles/r6_fused_threshold.json)
-  uint32_t fused_max_words = 1024;
-  uint8_t* d_fctl = nullptr;        // KsgWinRun[2], then the counters uint32[2][groups][8]
-  uint8_t* h_fctl = nullptr;        // pinned: the round's first slot and zeroed counters
-  double last_hus[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // host us per phase of the last batch (ksg_last_batch_host_us)
-  double totals[24] = {};  // ksg_batch_totals: the per-batch diagnostics summed over batches
-  int64_t max_cap = 0, min_cap = 0;
-
-  // Commits of the last ksg_schedule_batch not yet replayed into the host
-  // mirror: replayed while the next batch runs on the device, or before any
-  // call that reads the mirror (flush_deferred).
-  std::vector<ksg_pod> dfr_pods;
-  std::vector<uint32_t> dfr_ids;
-  std::vector<int32_t> dfr_out;
-  std::unordered_set<uint64_t> dfr_uids;
-  int64_t dfr_sum = 0;   // sum of the deferred pods' requests (cpu + memory), capped
-  bool dfr_neg = false;  // a deferred pod has a negative request
-  // calculateScore (priorities.go:27-37) stays in [0, 10] only while capacities lie in
-  // [0, 2^63 / 10] and requested totals are non-negative; score_bound() assumes that range.
-  // lr_wild: this node list, or a pod seen since ksg_set_cluster, can take a LeastRequested
-  // term out of it (a negative capacity or one whose x10 wraps, a negative request, a total
-  // that wraps): the int64 score kernels serve the context from then on (KsgDev.wide)
-  bool lr_wild = false;
-  int64_t used_hi = 0;                // the largest committed total the mirror has held
-  unsigned __int128 dfr_req = 0;      // requests of batches whose commits are not in the mirror yet
-
-  // extensions (ksg_set_extensions; exact kernels, one rank, parity unpinned)
-  bool ext_on = false;
-  ksg_ext_config ext{};
-  std::vector<int64_t> sc_used;  // [n_scalar][N] host mirror of scalar_used
-  std::unordered_map<uint64_t, std::array<int64_t, KSG_MAX_SCALAR>> ext_scalar;  // uid -> requests
-  const ksg_pod_ext* cur_ext = nullptr;  // the _ext entry point's records for this call
-  ksg_pod_ext* d_pext = nullptr;         // device copy (batch) / the single pod's (d_one_ext)
-  size_t pext_cap = 0;
-  ksg_pod_ext* d_one_ext = nullptr;
-
-  // the resident drop-in server (ksg_serve.hip): begin / commit as requests in
-  // mapped host memory instead of launches, copies and stream syncs
-  bool srv_enabled = true;      // KSG_SERVE=0: the launch-per-call path
-  bool srv_running = false;     // a server kernel may be resident on `st`
-  KsgSrvBox* srv_box = nullptr;   // pinned, coherent, mapped
-  KsgSrvBox* srv_dbox = nullptr;  // its device address
-  uint8_t* srv_fail = nullptr;    // fail codes of the shard's nodes (mapped)
-  uint8_t* srv_dfail = nullptr;
-  size_t srv_fail_cap = 0;
-  uint32_t srv_seq = 0;         // last request posted
-  uint64_t srv_idle_us = 20000; // the server returns after this long without a request
-  bool pend_srv = false;        // the pending begin was served by the server
-  uint32_t srv_bhdr[KSG_SRV_HDR_DW] = {};  // that begin's header (its payload layout)
-  std::vector<uint64_t> srv_tw;  // its tie words (node lo + 64 i + b), the commit picks from them
-  uint32_t srv_unacked = 0;      // a COMMIT posted without waiting for its answer (0: none)
-  uint32_t srv_served = 0;       // every request up to this one was served
-  uint32_t srv_last_ctl = 0;     // the last control request posted
-  bool srv_pext_on = false;      // the pending begin's extension record (its commit carries it)
-  ksg_pod_ext srv_pext{};
-  uint64_t srv_launches = 0;
-  bool srv_grid_on = true;       // KSG_SERVE_GRID=0: the one-workgroup server at every size
-  uint32_t srv_npt4_min = 16384;  // KSG_SERVE_GRID_NPT4_MIN: past this many nodes 4 nodes per thread
-  uint32_t srv_grid_min = 0;
-  bool srv_grid_ext = true;  // KSG_SERVE_GRID_EXT=0: extension contexts on the one-workgroup server  // KSG_SERVE_GRID_MIN: shards above this many nodes take the grid server
-                              // (it beats the one-workgroup server at 500 nodes already: 7.2 vs 10.9 us)
-  KsgSrvGrid* srv_grid = nullptr;  // its device state (+ the fail codes)
-  size_t srv_grid_cap = 0;
-  uint32_t srv_epoch = 0;
-  bool srv_stamps = false;      // KSG_SERVE_STAMPS=1: sum the server's per-stage cycles of each begin
-  int64_t srv_grid_opts = -1;   // KSG_SERVE_GRID_OPTS (KsgSrvArgs.grid_opts; -1: by size)
-  bool srv_debug = false;
-  unsigned __int128 static_mag = 0;  // max |score| of the terms ksg_set_static_terms added
-  // the node labels on the device (ksg_add_static_config evaluates more static terms from them)
-  const ksg_node* d_lbl_nodes = nullptr;
-  const uint32_t* d_lbl_pairs = nullptr;
-  const uint32_t* d_lbl_keys = nullptr;
-  bool srv_trace = false;       // KSG_SERVE_TRACE=1: every post, wait and relaunch to stderr       // KSG_SERVE_DEBUG=1: the grid server's stage markers, reported on a fault
-  double srv_stage[6] = {};     // (printed by ksg_destroy)
-  uint64_t srv_stamped = 0;
-
-  // begin/commit
-  bool pending = false;
-  uint64_t pending_k = 0;
-  ksg_pod pend{};
-  std::vector<uint32_t> pend_ids;
-
-  // Every entry point holds `mu`, so reflector threads may call ksg_add_pod /
-  // ksg_remove_pod while the scheduling thread schedules. Updates that arrive
-  // between ksg_schedule_begin and its commit are queued (validated first) and
-  // applied, in arrival order, when the pending pod is committed or abandoned:
-  // between pods, never inside one (SURVEY.md 8(b) "Threading").
-  std::recursive_mutex mu;
-  struct Queued {
-    bool add;
-    uint32_t host;
-    ksg_pod pod;
-    std::vector<uint32_t> ids;
-    uint64_t uid;
-  };
-  std::vector<Queued> upd_q;
-  std::unordered_set<uint64_t> q_added, q_removed;
-};
-
-#define KSG_LOCK(c) std::lock_guard<std::recursive_mutex> ksg_lock_((c)->mu)
-
-namespace {
 
 int fail(ksg_ctx* c, int code, const char* fmt, ...) {
   char buf[512];
@@ -364,21 +35,13 @@ int fail(ksg_ctx* c, int code, const char* fmt, ...) {
   return code;
 }
 
-#define HIPCHK(c, x)                                                                 \
-  do {                                                                               \
-    hipError_t e_ = (x);                                                             \
-    if (e_ != hipSuccess)                                                            \
-      return fail((c), KSG_ERR_HIP, "%s:%d %s: %s", __FILE__, __LINE__, #x,          \
-                  hipGetErrorString(e_));                                            \
-  } while (0)
+// File-local helpers, and the ones ksg_host.h declares for ksg_batch.cpp: none of them
+// is exported from the library.
+#pragma GCC visibility push(hidden)
 
-#define NCCLCHK(c, x)                                                                \
-  do {                                                                               \
-    ncclResult_t r_ = (x);                                                           \
-    if (r_ != ncclSuccess)                                                           \
-      return fail((c), KSG_ERR_RCCL, "%s:%d %s: %s", __FILE__, __LINE__, #x,         \
-                  ncclGetErrorString(r_));                                           \
-  } while (0)
+constexpr uint32_t kMaxNodesPerShard = KSG_R_MAX * KSG_NT;
+// ksg_explain_batch: device staging for the per-node codes of one chunk of pods
+constexpr size_t kExplainStageBytes = (size_t)64 << 20;
 
 template <typename T>
 int dalloc(ksg_ctx* c, T** p, size_t count, std::vector<void*>* owner) {
@@ -389,21 +52,19 @@ int dalloc(ksg_ctx* c, T** p, size_t count, std::vector<void*>* owner) {
   if (owner) owner->push_back(q);
   return KSG_OK;
 }
+// ... a fixed-size zeroed scratch buffer; the one it replaces is freed first
+template <typename T>
+int dalloc(ksg_ctx* c, DevBuf<T>& b, size_t count) {
+  b.release();
+  int rc = dalloc(c, &b.p, count, nullptr);
+  if (rc == KSG_OK) b.cap = std::max<size_t>(count, 1);
+  return rc;
+}
 
 void free_cluster(ksg_ctx* c) {
   for (void* p : c->cluster_allocs) (void)hipFree(p);
   c->cluster_allocs.clear();
   c->have_cluster = false;
-}
-
-int grow(ksg_ctx* c, void** p, size_t* cap, size_t need, size_t elem) {
-  if (need <= *cap && *p) return KSG_OK;
-  size_t nc = std::max<size_t>(need, std::max<size_t>(*cap * 2, 64));
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  HIPCHK(c, hipMalloc(p, nc * elem));
-  *cap = nc;
-  return KSG_OK;
 }
 
 int pick_R(uint32_t shard_nodes) {
@@ -432,7 +93,7 @@ int srv_flush_patches(ksg_ctx* c);
 int flush_patches(ksg_ctx* c) {
   if (c->patches.empty()) return KSG_OK;
   if (c->srv_running) return srv_flush_patches(c);
-  int rc = grow(c, (void**)&c->d_patch, &c->patch_cap, c->patches.size(), sizeof(KsgPatch));
+  int rc = c->d_patch.grow(c, c->patches.size());
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(c->d_patch, c->patches.data(), c->patches.size() * sizeof(KsgPatch),
                            hipMemcpyHostToDevice, c->st));
@@ -572,18 +233,15 @@ int check_pod(ksg_ctx* c, const ksg_pod* p, const uint32_t* ids, size_t n_ids) {
   return KSG_OK;
 }
 
-// upload one pod + its id list into the single-pod scratch slots
-int grow_host(ksg_ctx* c, uint8_t** p, size_t* cap, size_t need);
-
 int upload_pods(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint32_t* ids, size_t n_ids) {
-  int rc = grow(c, (void**)&c->d_pods, &c->pods_cap, n, sizeof(ksg_pod));
+  int rc = c->d_pods.grow(c, n);
   if (rc) return rc;
-  rc = grow(c, (void**)&c->d_ids, &c->ids_cap, std::max<size_t>(n_ids, 1), sizeof(uint32_t));
+  rc = c->d_ids.grow(c, std::max<size_t>(n_ids, 1));
   if (rc) return rc;
   // every caller synchronises the stream before it returns, so the staging
   // buffer is free again at the next call
   const size_t pb = (size_t)n * sizeof(ksg_pod), ib = n_ids * sizeof(uint32_t);
-  if ((rc = grow_host(c, &c->h_up, &c->h_up_cap, pb + ib))) return rc;
+  if ((rc = c->h_up.grow(c, pb + ib))) return rc;
   memcpy(c->h_up, pods, pb);
   if (n_ids) memcpy(c->h_up + pb, ids, ib);
   HIPCHK(c, hipMemcpyAsync(c->d_pods, c->h_up, pb, hipMemcpyHostToDevice, c->st));
@@ -597,9 +255,9 @@ int upload_one(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, size_t n_ids
   const size_t pb = (sizeof(ksg_pod) + 15) & ~(size_t)15, ib = std::max<size_t>(n_ids, 1) * sizeof(uint32_t);
   // (extensions: the pod's ksg_pod_ext after the ids, all-zero for the plain entry points)
   const size_t eo = (pb + ib + 15) & ~(size_t)15, eb = c->ext_on ? sizeof(ksg_pod_ext) : 0;
-  int rc = grow(c, (void**)&c->d_one, &c->one_cap, eo + eb, 1);
+  int rc = c->d_one.grow(c, eo + eb);
   if (rc) return rc;
-  if ((rc = grow_host(c, &c->h_up, &c->h_up_cap, eo + eb))) return rc;
+  if ((rc = c->h_up.grow(c, eo + eb))) return rc;
   memcpy(c->h_up, pod, sizeof(ksg_pod));
   if (n_ids) memcpy(c->h_up + pb, ids, n_ids * sizeof(uint32_t));
   if (eb) {
@@ -608,7 +266,7 @@ int upload_one(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, size_t n_ids
   }
   HIPCHK(c, hipMemcpyAsync(c->d_one, c->h_up, eb ? eo + eb : pb + (n_ids ? n_ids * sizeof(uint32_t) : 0),
                            hipMemcpyHostToDevice, c->st));
-  c->one_pod = reinterpret_cast<const ksg_pod*>(c->d_one);
+  c->one_pod = reinterpret_cast<const ksg_pod*>(c->d_one.p);
   c->one_ids = reinterpret_cast<const uint32_t*>(c->d_one + pb);
   c->d_one_ext = eb ? reinterpret_cast<ksg_pod_ext*>(c->d_one + eo) : nullptr;
   return KSG_OK;
@@ -642,23 +300,11 @@ size_t call_ids_extent(const ksg_ctx* c, const ksg_pod* p) {
 }
 
 // the shard records decide reads: all-gathered (exchange path) or this rank's own
-uint8_t* rec_buf(ksg_ctx* c) { return c->xchg ? c->d_rec_recv : c->d_rec_send; }
+uint8_t* rec_buf(ksg_ctx* c) { return c->xchg ? c->d_rec_recv.p : c->d_rec_send.p; }
 
 bool anti_on(const ksg_ctx* c) { return c->cfg.n_anti > 0 && c->dev.n_domains_total > 0; }
 
 // ---- cross-rank exchange: RCCL over xGMI, or the caller's host transport ----
-int grow_host(ksg_ctx* c, uint8_t** p, size_t* cap, size_t need) {
-  if (*cap >= need) return KSG_OK;
-  // geometric: a pinned (re)allocation costs ~0.2 ms (hipHostFree synchronises)
-  const size_t nc = std::max<size_t>(need, std::max<size_t>(*cap * 2, 4096));
-  if (*p) (void)hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  HIPCHK(c, hipHostMalloc((void**)p, nc, hipHostMallocDefault));
-  *cap = nc;
-  return KSG_OK;
-}
-
 // recv[g * bytes, (g + 1) * bytes) = rank g's send, on c->st
 int allgather(ksg_ctx* c, const void* dsend, void* drecv, size_t bytes) {
   if (c->comm) {
@@ -667,9 +313,7 @@ int allgather(ksg_ctx* c, const void* dsend, void* drecv, size_t bytes) {
   }
   if (!c->xfn) return fail(c, KSG_ERR_STATE, "sharded context has neither an RCCL communicator nor ksg_set_allgather");
   int rc;
-  if ((rc = grow_host(c, &c->h_xsend, &c->h_xsend_cap, bytes)) ||
-      (rc = grow_host(c, &c->h_xrecv, &c->h_xrecv_cap, bytes * c->world)))
-    return rc;
+  if ((rc = c->h_xsend.grow(c, bytes)) || (rc = c->h_xrecv.grow(c, bytes * c->world))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->h_xsend, dsend, bytes, hipMemcpyDeviceToHost, c->st));
   HIPCHK(c, hipStreamSynchronize(c->st));
   if ((rc = c->xfn(c->xuser, c->h_xsend, c->h_xrecv, (uint64_t)bytes)) != 0)
@@ -678,55 +322,31 @@ int allgather(ksg_ctx* c, const void* dsend, void* drecv, size_t bytes) {
   return KSG_OK;
 }
 
-int allreduce_sum_i32(ksg_ctx* c, const int32_t* dsend, int32_t* drecv, uint32_t n) {
+// drecv[i] = sum (wrapping, as ncclSum on int32) or max over the ranks of their dsend[i]
+int allreduce_i32(ksg_ctx* c, Reduce op, const int32_t* dsend, int32_t* drecv, uint32_t n) {
   if (c->comm) {
-    NCCLCHK(c, ncclAllReduce(dsend, drecv, n, ncclInt32, ncclSum, c->comm, c->st));
+    NCCLCHK(c, ncclAllReduce(dsend, drecv, n, ncclInt32, op == Reduce::Sum ? ncclSum : ncclMax, c->comm, c->st));
     return KSG_OK;
   }
   if (!c->xfn) return fail(c, KSG_ERR_STATE, "sharded context has neither an RCCL communicator nor ksg_set_allgather");
   const size_t bytes = (size_t)n * 4;
   int rc;
-  if ((rc = grow_host(c, &c->h_xsend, &c->h_xsend_cap, bytes)) ||
-      (rc = grow_host(c, &c->h_xrecv, &c->h_xrecv_cap, bytes * (c->world + 1))))
-    return rc;
+  if ((rc = c->h_xsend.grow(c, bytes)) || (rc = c->h_xrecv.grow(c, bytes * (c->world + 1)))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->h_xsend, dsend, bytes, hipMemcpyDeviceToHost, c->st));
   HIPCHK(c, hipStreamSynchronize(c->st));
   if ((rc = c->xfn(c->xuser, c->h_xsend, c->h_xrecv, (uint64_t)bytes)) != 0)
     return fail(c, KSG_ERR_RCCL, "allgather callback returned %d", rc);
-  int32_t* all = reinterpret_cast<int32_t*>(c->h_xrecv);
-  int32_t* sum = all + (size_t)n * c->world;
+  int32_t* all = reinterpret_cast<int32_t*>(c->h_xrecv.p);
+  int32_t* res = all + (size_t)n * c->world;
   for (uint32_t i = 0; i < n; ++i) {
-    uint32_t acc = 0;  // wrapping, as ncclSum on int32
-    for (int g = 0; g < c->world; ++g) acc += (uint32_t)all[(size_t)g * n + i];
-    sum[i] = (int32_t)acc;
+    uint32_t acc = (uint32_t)all[i];
+    for (int g = 1; g < c->world; ++g) {
+      const int32_t v = all[(size_t)g * n + i];
+      acc = op == Reduce::Sum ? acc + (uint32_t)v : (uint32_t)std::max((int32_t)acc, v);
+    }
+    res[i] = (int32_t)acc;
   }
-  HIPCHK(c, hipMemcpyAsync(drecv, sum, bytes, hipMemcpyHostToDevice, c->st));
-  return KSG_OK;
-}
-
-int allreduce_max_i32(ksg_ctx* c, const int32_t* dsend, int32_t* drecv, uint32_t n) {
-  if (c->comm) {
-    NCCLCHK(c, ncclAllReduce(dsend, drecv, n, ncclInt32, ncclMax, c->comm, c->st));
-    return KSG_OK;
-  }
-  if (!c->xfn) return fail(c, KSG_ERR_STATE, "sharded context has neither an RCCL communicator nor ksg_set_allgather");
-  const size_t bytes = (size_t)n * 4;
-  int rc;
-  if ((rc = grow_host(c, &c->h_xsend, &c->h_xsend_cap, bytes)) ||
-      (rc = grow_host(c, &c->h_xrecv, &c->h_xrecv_cap, bytes * (c->world + 1))))
-    return rc;
-  HIPCHK(c, hipMemcpyAsync(c->h_xsend, dsend, bytes, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(c, hipStreamSynchronize(c->st));
-  if ((rc = c->xfn(c->xuser, c->h_xsend, c->h_xrecv, (uint64_t)bytes)) != 0)
-    return fail(c, KSG_ERR_RCCL, "allgather callback returned %d", rc);
-  int32_t* all = reinterpret_cast<int32_t*>(c->h_xrecv);
-  int32_t* mx = all + (size_t)n * c->world;
-  for (uint32_t i = 0; i < n; ++i) {
-    int32_t m = all[i];
-    for (int g = 1; g < c->world; ++g) m = std::max(m, all[(size_t)g * n + i]);
-    mx[i] = m;
-  }
-  HIPCHK(c, hipMemcpyAsync(drecv, mx, bytes, hipMemcpyHostToDevice, c->st));
+  HIPCHK(c, hipMemcpyAsync(drecv, res, bytes, hipMemcpyHostToDevice, c->st));
   return KSG_OK;
 }
 
@@ -743,8 +363,8 @@ int scan_exchange(ksg_ctx* c, const ksg_pod* dpod, const uint32_t* dids, int mod
     HIPCHK(c, ksg_launch_scan(c->R, anti, c->dev, dpod, dids, mode, 1, nullptr, nullptr, c->d_rec_send,
                               c->d_dpart, nullptr, c->st, dext));
     const uint32_t D = c->dev.n_domains_total;
-    int rc = anti ? allreduce_sum_i32(c, c->d_dpart, c->d_dglobal, D) : KSG_OK;
-    if (!rc && tt) rc = allreduce_max_i32(c, c->d_dpart + D, c->d_dglobal + D, 1);
+    int rc = anti ? allreduce_i32(c, Reduce::Sum, c->d_dpart, c->d_dglobal, D) : KSG_OK;
+    if (!rc && tt) rc = allreduce_i32(c, Reduce::Max, c->d_dpart + D, c->d_dglobal + D, 1);
     if (rc) return rc;
     HIPCHK(c, ksg_launch_scan(c->R, anti, c->dev, dpod, dids, mode, 2, fail_out, score_out, c->d_rec_send,
                               nullptr, c->d_dglobal, c->st, dext));
@@ -759,76 +379,6 @@ int scan_exchange(ksg_ctx* c, const ksg_pod* dpod, const uint32_t* dids, int mod
     }  // (one rank: decide reads the record where the scan wrote it, rec_buf)
   }
   return KSG_OK;
-}
-
-// The window path needs scores that commits can only lower (see ksg_window.hip):
-// non-negative LeastRequested / ServiceSpreading weights and int64 totals far
-// from wrapping (ServiceAntiAffinity is handled by its count pass and stops).
-// The resolver walks the whole node set on every rank (state is replicated).
-KsgDev full_geometry(const ksg_ctx* c) {
-  KsgDev f = c->dev;
-  f.lo = 0;
-  f.hi = c->N;
-  f.wlo = 0;
-  f.nwords = c->nw;
-  return f;
-}
-
-bool use_window(ksg_ctx* c, const ksg_pod* pods, uint32_t n) {
-  if (c->window == 0 || c->nw > 32 * 64 || ksg_win_max_window(full_geometry(c)) < 8) return false;
-  // extensions: PodToleratesNodeTaints is static per (pod, node); extended
-  // resources only shrink under commits and the resolver re-checks them on the
-  // window's committed nodes like cpu / memory. With TaintToleration /
-  // BalancedAllocation scores the resolver re-scores the committed nodes (a
-  // BalancedAllocation score can RISE: ksg_plain.hip's risers and joiners); the
-  // TaintToleration term needs the node taints as one mask (max_taints <= 64).
-  // ServiceAntiAffinity, negative requests and requests past 2^16 take the exact
-  // kernels.
-  if (c->ext_on) {
-    // ServiceAntiAffinity with the extensions: the window path only for the static filters —
-    // PodToleratesNodeTaints, and extended resources no pod of the batch requests (a zero request
-    // fits whatever the node's usage) — with both extension scores off: the anti-affinity
-    // resolvers re-check nothing extension-specific on the window's committed nodes
-    if (anti_on(c)) {
-      if (c->ext.w_taint_toleration != 0 || c->ext.w_balanced != 0) return false;
-      if (c->cur_ext)
-        for (uint32_t i = 0; i < n; ++i)
-          for (uint32_t r = 0; r < c->ext.n_scalar; ++r)
-            if (c->cur_ext[i].scalar[r] != 0) return false;
-    }
-    if (c->ext.w_taint_toleration != 0 && !c->dev.ntaint) return false;
-    if (c->cur_ext)
-      for (uint32_t i = 0; i < n; ++i)
-        for (uint32_t r = 0; r < c->ext.n_scalar; ++r)
-          if (c->cur_ext[i].scalar[r] < 0 || c->cur_ext[i].scalar[r] > KSG_WIN_XREQ_BOUND) return false;
-  }
-  // int64 combined scores
-  if (c->dev.wide) return false;
-  // monotonicity under commits needs non-negative pod-dependent weights
-  if (c->cfg.w_least_requested < 0 || c->cfg.w_service_spreading < 0) return false;
-  // lr_win (ksg_device.h) is exact for 0 <= capacity, requested totals <= 2^49
-  const int64_t lim = KSG_WIN_LR_BOUND;
-  if (c->max_cap > lim || c->min_cap < 0) return false;
-  if (c->mu_dirty) {
-    c->mu_max = 0;
-    c->mu_neg = false;
-    for (uint32_t i = 0; i < c->N; ++i) {
-      c->mu_neg |= c->used_c[i] < 0 || c->used_m[i] < 0;
-      c->mu_max = std::max<int64_t>(c->mu_max, std::max<int64_t>(c->used_c[i], c->used_m[i]));
-    }
-    c->mu_dirty = false;
-  }
-  if (c->mu_neg) return false;
-  const int64_t mu = c->mu_max;
-  // commits not yet in the mirror (non-negative: checked by the caller) only add
-  int64_t sum = c->dfr_sum;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (pods[i].milli_cpu < 0 || pods[i].memory < 0) return false;
-    // (each operand clamped first: two requests of 2^62 overflow the signed add)
-    sum += std::min<int64_t>(std::min<int64_t>(pods[i].milli_cpu, lim) + std::min<int64_t>(pods[i].memory, lim), lim);
-    if (sum > lim) return false;
-  }
-  return mu + sum <= lim;
 }
 
 // |combined score| bound of a weight set: 10 * sum |w| over the score-10
@@ -867,8 +417,6 @@ int flush_deferred(ksg_ctx* c) {
   drop_deferred(c);
   return rc;
 }
-
-int ensure_out(ksg_ctx* c, size_t n) { return grow(c, (void**)&c->d_out, &c->out_cap, n, sizeof(int32_t)); }
 
 // Waits for the stream's work so far. The batch path's host thread has nothing
 // left to do at this point, so it polls an event instead of sleeping in
@@ -1239,7 +787,7 @@ bool srv_put_pod(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, size_t n_i
   return true;
 }
 
-}  // namespace
+#pragma GCC visibility pop
 
 extern "C" {
 
@@ -1327,17 +875,17 @@ static int create_impl(const ksg_config* cfg, int device, int rank, int world, c
       (e = hipEventCreateWithFlags(&c->ev1, kTimingEvent)) != hipSuccess ||
       (e = hipEventCreateWithFlags(&c->ev_wait, hipEventDisableTiming)) != hipSuccess)
     return bail(fail(c, KSG_ERR_HIP, "stream/event: %s", hipGetErrorString(e)));
-  c->spin_wait = !(getenv("KSG_SPIN_WAIT") && atoi(getenv("KSG_SPIN_WAIT")) == 0);
-  c->srv_enabled = !(getenv("KSG_SERVE") && atoi(getenv("KSG_SERVE")) == 0);
-  c->srv_stamps = getenv("KSG_SERVE_STAMPS") && atoi(getenv("KSG_SERVE_STAMPS")) != 0;
-  c->srv_debug = getenv("KSG_SERVE_DEBUG") && atoi(getenv("KSG_SERVE_DEBUG")) != 0;
-  c->srv_trace = getenv("KSG_SERVE_TRACE") && atoi(getenv("KSG_SERVE_TRACE")) != 0;
+  c->spin_wait = env_flag("KSG_SPIN_WAIT", true);
+  c->srv_enabled = env_flag("KSG_SERVE", true);
+  c->srv_stamps = env_flag("KSG_SERVE_STAMPS", false);
+  c->srv_debug = env_flag("KSG_SERVE_DEBUG", false);
+  c->srv_trace = env_flag("KSG_SERVE_TRACE", false);
   if (const char* go = getenv("KSG_SERVE_GRID_OPTS")) c->srv_grid_opts = (int64_t)strtoul(go, nullptr, 0);
-  if (const char* iu = getenv("KSG_SERVE_IDLE_US")) c->srv_idle_us = (uint64_t)std::max(atoll(iu), 1LL);
-  c->srv_grid_on = !(getenv("KSG_SERVE_GRID") && atoi(getenv("KSG_SERVE_GRID")) == 0);
-  if (const char* gm = getenv("KSG_SERVE_GRID_MIN")) c->srv_grid_min = (uint32_t)std::max(atoi(gm), 0);
-  if (const char* g4 = getenv("KSG_SERVE_GRID_NPT4_MIN")) c->srv_npt4_min = (uint32_t)std::max(atoi(g4), 0);
-  c->srv_grid_ext = !(getenv("KSG_SERVE_GRID_EXT") && atoi(getenv("KSG_SERVE_GRID_EXT")) == 0);
+  c->srv_idle_us = (uint64_t)env_int("KSG_SERVE_IDLE_US", (int64_t)c->srv_idle_us, 1, INT64_MAX);
+  c->srv_grid_on = env_flag("KSG_SERVE_GRID", true);
+  c->srv_grid_min = (uint32_t)env_int("KSG_SERVE_GRID_MIN", c->srv_grid_min, 0, INT32_MAX);
+  c->srv_npt4_min = (uint32_t)env_int("KSG_SERVE_GRID_NPT4_MIN", c->srv_npt4_min, 0, INT32_MAX);
+  c->srv_grid_ext = env_flag("KSG_SERVE_GRID_EXT", true);
   if (const char* rm = getenv("KSG_ROUND_MARGIN")) c->round_margin = std::min(std::max(atof(rm), 0.5), 4.0);
   // The exchange path (shard scan, all-gather of per-shard records, replicated
   // resolve) runs for world > 1, and for a 1-rank RCCL communicator when the caller
@@ -1353,21 +901,20 @@ static int create_impl(const ksg_config* cfg, int device, int rank, int world, c
     }
   }
   int rc;
-  if (const char* wenv = getenv("KSG_WINDOW")) c->window = (uint32_t)atoi(wenv);
-  if (const char* kev = getenv("KSG_KERNEL_EVENTS")) c->ev_stride = (uint32_t)std::max(atoi(kev), 0);
-  if ((rc = dalloc(c, &c->d_rng, 1, nullptr)) || (rc = dalloc(c, &c->d_summary, 4, nullptr)) ||
-      (rc = dalloc(c, &c->d_run, 1, nullptr)))
+  c->window = (uint32_t)env_int("KSG_WINDOW", c->window, INT32_MIN, INT32_MAX);
+  c->ev_stride = (uint32_t)env_int("KSG_KERNEL_EVENTS", c->ev_stride, 0, INT32_MAX);
+  if ((rc = dalloc(c, c->d_rng, 1)) || (rc = dalloc(c, c->d_summary, 4)) || (rc = dalloc(c, c->d_run, 1)))
     return bail(rc);
   if ((e = hipHostMalloc((void**)&c->h_run, sizeof(KsgWinRun), hipHostMallocDefault)) != hipSuccess)
     return bail(fail(c, KSG_ERR_HIP, "hipHostMalloc: %s", hipGetErrorString(e)));
-  c->win_fused = !(getenv("KSG_FUSED") && atoi(getenv("KSG_FUSED")) == 0);
+  c->win_fused = env_flag("KSG_FUSED", true);
   {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 16) cus = 0;
     c->fused_grid = (uint32_t)cus;
-    if (const char* fg = getenv("KSG_FUSED_GRID")) c->fused_grid = (uint32_t)std::min(std::max(atoi(fg), 9), 4096);
+    c->fused_grid = (uint32_t)env_int("KSG_FUSED_GRID", c->fused_grid, 9, 4096);
     if (c->fused_grid == 0) c->win_fused = false;
-    if (const char* fw = getenv("KSG_FUSED_MAX_WORDS")) c->fused_max_words = (uint32_t)std::max(atoi(fw), 0);
+    c->fused_max_words = (uint32_t)env_int("KSG_FUSED_MAX_WORDS", c->fused_max_words, 0, INT32_MAX);
   }
   if ((e = hipMalloc((void**)&c->d_fctl, kFctlBytes)) != hipSuccess ||
       (e = hipHostMalloc((void**)&c->h_fctl, kFctlBytes, hipHostMallocDefault)) != hipSuccess)
@@ -1420,24 +967,14 @@ int ksg_destroy(ksg_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->st) (void)hipStreamSynchronize(c->st);
   free_cluster(c);
-  void* scratch[] = {c->d_pods, c->d_ids, c->d_fail, c->d_score, c->d_rec_send, c->d_rec_recv, c->d_dpart,
-                     c->d_dglobal, c->d_out, c->d_rng, c->d_summary, c->d_patch, c->d_shard_wlo,
-                     c->d_winsum, c->d_xsend, c->d_xrecv, c->d_run, c->d_dcnt, c->d_admit, c->d_one,
-                     c->d_t0img, c->d_draws, c->d_etmax, c->d_epsoft, c->d_ethist, c->d_xcodes, c->d_xhist};
-  for (void* p : scratch)
-    if (p) (void)hipFree(p);
   if (c->comm) ncclCommDestroy(c->comm);
-  if (c->h_xsend) (void)hipHostFree(c->h_xsend);
   if (c->h_run) (void)hipHostFree(c->h_run);
   if (c->h_fctl) (void)hipHostFree(c->h_fctl);
   if (c->d_fctl) (void)hipFree(c->d_fctl);
-  if (c->h_up) (void)hipHostFree(c->h_up);
-  if (c->h_dn) (void)hipHostFree(c->h_dn);
   if (c->h_map) (void)hipHostFree(c->h_map);
   if (c->srv_box) (void)hipHostFree(c->srv_box);
   if (c->srv_grid) (void)hipFree(c->srv_grid);
   if (c->srv_fail) (void)hipHostFree(c->srv_fail);
-  if (c->h_xrecv) (void)hipHostFree(c->h_xrecv);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev_wait) (void)hipEventDestroy(c->ev_wait);
@@ -1446,7 +983,7 @@ int ksg_destroy(ksg_ctx* c) {
   for (auto& e : c->wev)
     if (e) (void)hipEventDestroy(e);
   if (c->st) (void)hipStreamDestroy(c->st);
-  delete c;
+  delete c;  // (the scratch buffers free themselves: the device is set and the stream was synchronised above)
   return KSG_OK;
 }
 
@@ -1610,7 +1147,7 @@ int ksg_set_cluster(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const u
   c->d_zmap = nullptr;
   uint32_t rr_dz = 0;
   if (c->cfg.n_anti == 1 && c->cfg.w_anti[0] != 0 && c->D > 0 && c->D + 1 <= KSG_RR_MAXZ && c->world == 1 &&
-      n_services <= KSG_RR_MAXSVC && !(getenv("KSG_DEBUG") && (atoi(getenv("KSG_DEBUG")) & 2048))) {
+      n_services <= KSG_RR_MAXSVC && !(env_int("KSG_DEBUG", 0, INT32_MIN, INT32_MAX) & 2048)) {
     rr_dz = c->D + 1;
     if ((rc = dalloc(c, &c->d_zmap, (size_t)rr_dz * std::max<uint32_t>(c->nw, 1), owner))) return rc;
     HIPCHK(c, ksg_launch_zonemap(n_nodes, anti_dom, c->D, c->nw, c->d_zmap, c->st));
@@ -1663,14 +1200,16 @@ int ksg_set_cluster(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const u
   bool any_pref = false;
   for (uint32_t q = 0; q < c->cfg.n_label_pref; ++q) any_pref |= c->cfg.w_pref[q] != 0;
   d.has_static_score = (c->cfg.w_equal != 0 || any_pref) ? 1 : 0;
-  d.dbg = getenv("KSG_DEBUG") ? atoi(getenv("KSG_DEBUG")) : 0;
+  d.dbg = (int)env_int("KSG_DEBUG", 0, INT32_MIN, INT32_MAX);
   // KSG_DEBUG bit 22 / 23: the next COMMIT / BEGIN posted to the resident server carries an
   // out-of-range payload layout (tests/test_gpu_serve.py: the server must reject it, not fault)
   c->dbg_corrupt = ((uint32_t)d.dbg >> 22) & 3u;
-  c->win_d1 = !(getenv("KSG_WIN_D1") && atoi(getenv("KSG_WIN_D1")) == 0);
+  c->win_d1 = env_flag("KSG_WIN_D1", true);
   if (d.dbg & (8 | 32 | 64)) {  // (32: the plain resolver's inconsistency record, ksg_plain.hip; 64: phase-A stamps)
-    (void)hipMalloc(&d.dbgbuf, KSG_DEBUG_COUNTER_WORDS * sizeof(int32_t));
-    (void)hipMemset(d.dbgbuf, 0, KSG_DEBUG_COUNTER_WORDS * sizeof(int32_t));
+    c->dbgbuf.release();  // (the previous node list's)
+    (void)hipMalloc((void**)&c->dbgbuf.p, KSG_DEBUG_COUNTER_WORDS * sizeof(int32_t));
+    (void)hipMemset(c->dbgbuf.p, 0, KSG_DEBUG_COUNTER_WORDS * sizeof(int32_t));
+    d.dbgbuf = c->dbgbuf.p;
   }
   d.has_static_fit = ((c->cfg.predicates & KSG_PRED_LABELSPRESENCE) && c->cfg.n_presence > 0) ? 1 : 0;
   d.cap_cpu = cap_c;
@@ -1709,23 +1248,12 @@ int ksg_set_cluster(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const u
 
   // scratch sized for the shard
   c->rec_bytes = (uint32_t)(sizeof(KsgRecordHdr) + (size_t)std::max<uint32_t>(c->nwords_max, 1) * 8);
-  if (c->d_rec_send) (void)hipFree(c->d_rec_send);
-  if (c->d_rec_recv) (void)hipFree(c->d_rec_recv);
-  if (c->d_fail) (void)hipFree(c->d_fail);
-  if (c->d_score) (void)hipFree(c->d_score);
-  if (c->d_dpart) (void)hipFree(c->d_dpart);
-  if (c->d_dglobal) (void)hipFree(c->d_dglobal);
-  if (c->d_shard_wlo) (void)hipFree(c->d_shard_wlo);
-  c->d_rec_send = c->d_rec_recv = c->d_fail = nullptr;
-  c->d_score = nullptr;
-  c->d_dpart = c->d_dglobal = nullptr;
-  c->d_shard_wlo = nullptr;
-  if ((rc = dalloc(c, &c->d_rec_send, c->rec_bytes, nullptr)) ||
-      (rc = dalloc(c, &c->d_rec_recv, (size_t)c->rec_bytes * c->world, nullptr)) ||
-      (rc = dalloc(c, &c->d_fail, NN, nullptr)) || (rc = dalloc(c, &c->d_score, NN, nullptr)) ||
-      (rc = dalloc(c, &c->d_dpart, (size_t)c->dev.n_domains_total + 1, nullptr)) ||  // (+ the TaintToleration max)
-      (rc = dalloc(c, &c->d_dglobal, (size_t)c->dev.n_domains_total + 1, nullptr)) ||
-      (rc = dalloc(c, &c->d_shard_wlo, c->world, nullptr)))
+  if ((rc = dalloc(c, c->d_rec_send, c->rec_bytes)) ||
+      (rc = dalloc(c, c->d_rec_recv, (size_t)c->rec_bytes * c->world)) ||
+      (rc = dalloc(c, c->d_fail, NN)) || (rc = dalloc(c, c->d_score, NN)) ||
+      (rc = dalloc(c, c->d_dpart, (size_t)c->dev.n_domains_total + 1)) ||  // (+ the TaintToleration max)
+      (rc = dalloc(c, c->d_dglobal, (size_t)c->dev.n_domains_total + 1)) ||
+      (rc = dalloc(c, c->d_shard_wlo, c->world)))
     return rc;
   HIPCHK(c, hipMemcpyAsync(c->d_shard_wlo, c->shard_wlo_h.data(), c->world * 4, hipMemcpyHostToDevice, c->st));
   HIPCHK(c, hipStreamSynchronize(c->st));
@@ -1850,7 +1378,7 @@ static int add_pod_impl(ksg_ctx* c, uint32_t host_id, const ksg_pod* pod, const 
   return KSG_OK;
 }
 
-static int remove_pod_impl(ksg_ctx* c, uint64_t uid) {
+int remove_pod_impl(ksg_ctx* c, uint64_t uid) {
   if (c->diverged) return cluster_ok(c);
   if (int rc0 = flush_deferred(c)) return rc0;
   auto it = c->pods.find(uid);
@@ -2032,7 +1560,7 @@ int ksg_schedule_begin(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, int6
   int64_t summ[3];
   const size_t nf = fail_codes ? (size_t)(c->hi - c->lo) : 0;
   if (nf) {
-    if ((rc = grow_host(c, &c->h_dn, &c->h_dn_cap, nf))) return rc;
+    if ((rc = c->h_dn.grow(c, nf))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->h_dn, c->d_fail, nf, hipMemcpyDeviceToHost, c->st));
   }
   HIPCHK(c, hipStreamSynchronize(c->st));
@@ -2104,423 +1632,6 @@ int ksg_schedule_commit(ksg_ctx* c, uint32_t tie_index, int32_t* out_node) {
   return KSG_OK;
 }
 
-int ksg_schedule_batch(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint32_t* ids, uint32_t n_ids,
-                       uint64_t* rng_state, int32_t* out_nodes) {
-  if (!c || (n && (!pods || !out_nodes)) || !rng_state) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
-  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
-  if (int rs = cluster_ok(c)) return rs;
-  HIPCHK(c, hipSetDevice(c->device));
-  c->last_ms = 0.0;
-  if (n == 0) return KSG_OK;
-  if (c->N == 0) {
-    for (uint32_t i = 0; i < n; ++i) out_nodes[i] = KSG_OUT_NONODES;
-    return KSG_OK;
-  }
-  // host time per phase (ksg_last_batch_host_us)
-  for (double& v : c->last_hus) v = 0.0;
-  auto t_last = std::chrono::steady_clock::now();
-  auto hphase = [&](int k) {
-    const auto t = std::chrono::steady_clock::now();
-    c->last_hus[k] += std::chrono::duration<double, std::micro>(t - t_last).count();
-    t_last = t;
-  };
-  for (uint32_t i = 0; i < n; ++i) {
-    int rc = check_pod(c, pods + i, ids, n_ids);
-    if (rc) return rc;
-    if (c->pods.count(pods[i].uid) || c->dfr_uids.count(pods[i].uid))
-      return fail(c, KSG_ERR_ARG, "pod %u: duplicate uid", i);
-  }
-  hphase(0);
-  int rc;
-  if ((rc = note_requests(c, pods, n))) return rc;
-  if (c->dfr_neg && (rc = flush_deferred(c))) return rc;
-  if ((rc = flush_patches(c))) return rc;
-  if ((rc = upload_pods(c, pods, n, ids, n_ids))) return rc;
-  if ((rc = ensure_out(c, n))) return rc;
-  // the placements and the generator state come back through pinned staging
-  // (a pageable copy-out blocks the host until the stream drains); the window
-  // path enqueues them with each round, which usually ends the batch, so the
-  // host waits for the device once per batch
-  const size_t dn_rng = ((size_t)n * 4 + 7) & ~(size_t)7;
-  if ((rc = grow_host(c, &c->h_dn, &c->h_dn_cap, dn_rng + 8))) return rc;
-  bool tail_queued = false;
-  auto enqueue_tail = [&]() -> int {
-    HIPCHK(c, hipEventRecord(c->ev1, c->st));
-    HIPCHK(c, hipMemcpyAsync(c->h_dn, c->d_out, (size_t)n * 4, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipMemcpyAsync(c->h_dn + dn_rng, c->d_rng, 8, hipMemcpyDeviceToHost, c->st));
-    return KSG_OK;
-  };
-  // Host work that overlaps the device: the previous batch's mirror replay, then
-  // this batch's deferred-replay inputs (pods, ids, every uid: the few pods that
-  // find no node are taken out again after the wait)
-  // (stashed into locals: they become the context's deferred replay only when
-  // the batch succeeds; a failure after the device work started leaves the
-  // context diverged until ksg_set_cluster)
-  bool stashed = false, dup_any = false;
-  std::vector<ksg_pod> st_pods;
-  std::vector<uint32_t> st_ids;
-  std::unordered_set<uint64_t> st_uids;
-  auto overlap_work = [&]() -> int {
-    if (stashed) return KSG_OK;
-    int rc2 = flush_deferred(c);
-    if (rc2) return rc2;
-    hphase(4);
-    st_pods.assign(pods, pods + n);
-    st_ids.assign(ids, ids + n_ids);
-    st_uids.swap(c->dfr_uids);  // (empty after the flush: keeps its buckets)
-    st_uids.reserve(2 * (size_t)n);
-    for (uint32_t i = 0; i < n; ++i) dup_any |= !st_uids.insert(pods[i].uid).second;
-    stashed = true;
-    hphase(7);
-    return KSG_OK;
-  };
-  struct DivergeGuard {
-    ksg_ctx* c;
-    bool armed = false;
-    ~DivergeGuard() {
-      if (armed) {
-        drop_deferred(c);
-        c->diverged = true;
-      }
-    }
-  } guard{c};
-  if (c->dev.dbg & 16384) c->dbg_fail_next = true;  // KSG_DEBUG & 16384: fail the batch after its device work
-  guard.armed = true;  // device work from here on
-  HIPCHK(c, hipMemcpyAsync(c->d_rng, rng_state, 8, hipMemcpyHostToDevice, c->st));
-  HIPCHK(c, hipEventRecord(c->ev0, c->st));
-  c->last_stats[0] = c->last_stats[1] = c->last_stats[2] = c->last_stats[3] = 0;
-  c->last_kms[0] = c->last_kms[1] = c->last_kms[2] = c->last_t0ms = 0;
-  c->last_wsum = 0;
-  hphase(1);
-  const ksg_pod_ext* dext = nullptr;
-  if (c->ext_on) {  // extensions: each pod's record (all-zero for the plain entry point)
-    if ((rc = grow(c, (void**)&c->d_pext, &c->pext_cap, n, sizeof(ksg_pod_ext)))) return rc;
-    if (c->cur_ext) {
-      HIPCHK(c, hipMemcpyAsync(c->d_pext, c->cur_ext, (size_t)n * sizeof(ksg_pod_ext), hipMemcpyHostToDevice, c->st));
-    } else {
-      HIPCHK(c, hipMemsetAsync(c->d_pext, 0, (size_t)n * sizeof(ksg_pod_ext), c->st));
-    }
-    dext = c->d_pext;
-  }
-  if (use_window(c, pods, n)) {
-    // Window path. Phase A scores the window on this rank's shard; with world > 1
-    // the per-word results are all-gathered once per window (not per pod) and
-    // every rank runs the same resolver over the whole replicated node state, so
-    // every rank commits the same pods to the same nodes.
-    const KsgDev full = full_geometry(c);
-    uint32_t W = std::min(c->window, ksg_win_max_window(full));
-    // Phase A scores all W pods of a window whatever the resolver gets through.
-    // Where windows stop early (ServiceAntiAffinity: every ~13 pods on config 4)
-    // the capacity follows the pods per window measured on earlier batches: 3x
-    // that, in pod groups of 8, at least 16. (A sharded context keeps W: every
-    // rank must size its launches alike, and its estimate restarts each batch.)
-    if (!c->xchg && c->ppw_est > 0.0) {
-      const uint32_t want = ((uint32_t)std::ceil(3.0 * c->ppw_est) + 7u) & ~7u;
-      W = std::min(W, std::max<uint32_t>(want, 16u));
-    }
-    KsgWinXchg x{};
-    x.exts = dext;  // (extensions: the filters, and the scores when esc)
-    x.ostride = std::max<uint32_t>(c->nwords_max, 1);
-    x.wcap = W;
-    x.world = (uint32_t)c->world;
-    for (int g = 0; g < c->world; ++g) {
-      uint32_t a, b;
-      ksg_shard_words(c->nw, (uint32_t)g, (uint32_t)c->world, &a, &b);
-      x.wlo[g] = a;
-      x.nw[g] = b - a;
-    }
-    const bool anti = anti_on(c);
-    const bool rr = anti && c->dev.rr_dz != 0 && c->d_zmap;  // ServiceAntiAffinity re-rank
-    const size_t fit_off = ((size_t)W * x.ostride * 12 + 7) & ~(size_t)7;
-    // (the domain counts are zeroed once here, then by each resolver for the next window)
-    x.fit_off = anti ? (uint32_t)fit_off : 0u;
-    x.b_off = rr ? (uint32_t)(fit_off + (size_t)W * x.ostride * 8) : 0u;
-    // extension scores on the plain resolver: the pods' fit bitmaps at the same offset
-    const bool esc = c->ext_on && (c->ext.w_taint_toleration != 0 || c->ext.w_balanced != 0);
-    const bool etm = esc && c->ext.w_taint_toleration != 0;  // (the TaintToleration count pass)
-    x.esc = esc ? 1u : 0u;
-    x.efit_off = esc ? (uint32_t)fit_off : 0u;
-    // the plain resolver without extensions up to 16,384 nodes (its ring holds the bitmaps):
-    // phase A's single-commit drop bitmaps at the same offset
-    const bool d1 = !anti && !dext && c->win_d1 && c->nw <= 4 * 64;
-    x.d1 = d1 ? 1u : 0u;
-    x.d1_off = d1 ? (uint32_t)fit_off : 0u;
-    x.blk = ((rr                  ? fit_off + (size_t)W * x.ostride * 16
-              : anti || esc || d1 ? fit_off + (size_t)W * x.ostride * 8
-                                  : (size_t)W * x.ostride * 12) +
-             255) & ~(size_t)255;
-    if (esc) {
-      if ((rc = grow(c, (void**)&c->d_etmax, &c->etmax_cap, W, sizeof(int32_t))) ||
-          (rc = grow(c, (void**)&c->d_ethist, &c->ethist_cap, (size_t)W * KSG_TBINS, sizeof(int32_t))) ||
-          (rc = grow(c, (void**)&c->d_epsoft, &c->epsoft_cap, W, sizeof(uint64_t))))
-        return rc;
-      // (zero once here; each resolver zeroes them again for the next window's count pass)
-      HIPCHK(c, hipMemsetAsync(c->d_etmax, 0, (size_t)W * sizeof(int32_t), c->st));
-      HIPCHK(c, hipMemsetAsync(c->d_ethist, 0, (size_t)W * KSG_TBINS * sizeof(int32_t), c->st));
-      x.tmax = c->d_etmax;
-      x.thist = c->d_ethist;
-      x.psoft = c->d_epsoft;
-    }
-    const size_t dcnt_n = (size_t)W * std::max<uint32_t>(c->D, 1);
-    if (anti) {
-      if ((rc = grow(c, (void**)&c->d_dcnt, &c->dcnt_cap, dcnt_n, sizeof(int32_t)))) return rc;
-      HIPCHK(c, hipMemsetAsync(c->d_dcnt, 0, dcnt_n * sizeof(int32_t), c->st));
-      x.dcnt = c->d_dcnt;
-      x.dcnt_n = (uint32_t)dcnt_n;
-    }
-    if (rr) {  // (the resolver resets the row bests to KSG_S32_NONE and the B counts to 0 for the next window)
-      const size_t dmb_n = (size_t)W * c->dev.rr_dz;  // [W][dz] row bests, then [W][dz] B nodes per row
-      if ((rc = grow(c, (void**)&c->d_dmb, &c->dmb_cap, 2 * dmb_n, sizeof(int32_t)))) return rc;
-      HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->d_dmb, (int)0x80000000, dmb_n, c->st));
-      HIPCHK(c, hipMemsetAsync(c->d_dmb + dmb_n, 0, dmb_n * sizeof(int32_t), c->st));
-      x.rr = 1;
-      x.dz = c->dev.rr_dz;
-      x.dmb = c->d_dmb;
-      x.zmap = c->d_zmap;
-    }
-    if ((rc = grow(c, (void**)&c->d_winsum, &c->win_cap, W, sizeof(KsgWinSum)))) return rc;
-    if ((rc = grow(c, (void**)&c->d_xsend, &c->xsend_cap, x.blk, 1))) return rc;
-    if (c->xchg && (rc = grow(c, (void**)&c->d_xrecv, &c->xrecv_cap, x.blk * c->world, 1))) return rc;
-    x.buf = c->xchg ? c->d_xrecv : c->d_xsend;
-    const bool plain = !anti;  // the plain resolver reads T0 images
-    if (plain) {
-      x.img_stride = ksg_win_t0_stride(full);
-      if ((rc = grow(c, (void**)&c->d_t0img, &c->t0img_cap, (size_t)W * x.img_stride, 1))) return rc;
-      x.img = c->d_t0img;
-    }
-    // one launch per window (KsgFused): one rank, no ServiceAntiAffinity, no extensions
-    const uint32_t fgroups = plain && !c->xchg && !dext && c->win_fused && full.nwords <= c->fused_max_words &&
-                                     ksg_win_fused_ok(full)
-                                 ? ksg_win_fused_groups(full, W) : 0u;
-    const bool fused = fgroups > 0 && fgroups <= kFctlGroups;
-    KsgWinRun* const fruns = reinterpret_cast<KsgWinRun*>(c->d_fctl);
-    uint32_t* const fcnt = reinterpret_cast<uint32_t*>(c->d_fctl + kFctlRuns);
-    uint64_t* wbits = reinterpret_cast<uint64_t*>(c->d_xsend);
-    int32_t* wmax = reinterpret_cast<int32_t*>(c->d_xsend + (size_t)W * x.ostride * 8);
-    // Windows are chained on the device: each kernel reads the window's start
-    // from d_run (written by the previous resolver), so the host enqueues a
-    // round of windows and synchronises once per round, not once per window.
-    // Windows per round: from the pods per window the previous rounds resolved
-    // (windows stop early on service / exhaustion / slot events, e.g. every ~13
-    // pods with ServiceAntiAffinity), 10% over; launches past the batch's end
-    // return at once. Fewer rounds = fewer host synchronisations per batch.
-    // A sharded context issues one collective per launch, so every rank must
-    // enqueue the same number of launches: its estimate starts fresh each batch
-    // and follows only this batch's progress, which every rank resolves alike.
-    double ppw_est = c->xchg ? 0.0 : c->ppw_est;
-    auto round_k = [&](uint32_t left) -> uint32_t {
-      const double ppw = ppw_est > 0.0 ? std::min<double>(std::max(ppw_est, 1.0), (double)W) : 0.8 * W;
-      const double k = std::ceil((double)left / ppw * c->round_margin) + 1.0;
-      return (uint32_t)std::min(k, 8192.0);
-    };
-    uint32_t pos = 0, K = round_k(n);
-    c->last_kms[0] = c->last_kms[1] = c->last_kms[2] = c->last_t0ms = 0;
-    c->last_wsum = 0;
-    hphase(2);
-    while (pos < n) {
-      if (c->wev.size() < 3 * (size_t)K + 1) {
-        const size_t old = c->wev.size();
-        c->wev.resize(3 * (size_t)K + 1, nullptr);
-        for (size_t i = old; i < c->wev.size(); ++i) HIPCHK(c, hipEventCreateWithFlags(&c->wev[i], kTimingEvent));
-      }
-      // the sampled launches rotate from round to round (launches k with
-      // (k + ev_off) % es == 0), so every position in a round, the no-op
-      // launches after the batch's end included, is timed equally often
-      const uint32_t es = std::min(c->ev_stride, K);  // (a short round still times one launch)
-      const uint32_t ev_off = es ? c->ev_phase++ % es : 0u;
-      *c->h_run = KsgWinRun{pos, n, 0, 0, {0, 0, 0, 0}};
-      if (fused) {  // slot 0 and both counter sets (the launches zero the next set as they go)
-        *reinterpret_cast<KsgWinRun*>(c->h_fctl) = *c->h_run;
-        HIPCHK(c, hipMemcpyAsync(c->d_fctl, c->h_fctl, kFctlRuns + (size_t)2 * fgroups * 8 * sizeof(uint32_t),
-                                 hipMemcpyHostToDevice, c->st));
-      } else {
-        HIPCHK(c, hipMemcpyAsync(c->d_run, c->h_run, sizeof(KsgWinRun), hipMemcpyHostToDevice, c->st));
-      }
-      HIPCHK(c, hipEventRecord(c->wev[0], c->st));
-      for (uint32_t k = 0; k < K; ++k) {
-        // HIP events on this stream around the sampled launches (per-kernel device time)
-        const bool evk = es && (k + ev_off) % es == 0;
-        // (launch k: events 3k before phase A, 3k+1 after it, 3k+2 before the resolver, 3k+3 =
-        // the next launch's 3(k+1) after it; the fused launch: 3k before it, 3k+3 after it)
-        if (evk && k > 0) HIPCHK(c, hipEventRecord(c->wev[3 * k], c->st));
-        if (fused) {
-          // the counter rows: fgroups per set, set k & 1 (the host zeroed both for launch 0; each
-          // launch's block 0 zeroes the other set for the next launch)
-          KsgFused f{c->d_pods, c->d_ids, fruns + ((k + 1) & 1), fcnt, k & 1u, fgroups};
-          HIPCHK(c, ksg_launch_win_fused(full, W, fruns + (k & 1), c->d_winsum, x, c->d_rng, c->d_out, f,
-                                         c->fused_grid, c->st));
-          if (evk) HIPCHK(c, hipEventRecord(c->wev[3 * k + 3], c->st));
-          continue;
-        }
-        if (anti) {
-          // ServiceAntiAffinity: the pods' per-domain counts over their filtered nodes first
-          // (into d_dcnt, zero: the previous resolver cleared it)
-          HIPCHK(c, ksg_launch_win_eval(c->dev, 1, c->d_pods, c->d_ids, c->d_run, W, c->d_winsum, wbits, wmax,
-                                        x.ostride, c->d_dcnt, nullptr, x.dmb, nullptr, x.dz, c->st, dext));
-          if (c->xchg && (rc = allreduce_sum_i32(c, c->d_dcnt, c->d_dcnt, (uint32_t)dcnt_n))) return rc;
-        }
-        if (etm) {  // TaintToleration: each pod's max soft-taint count over its filtered nodes first
-          HIPCHK(c, ksg_launch_win_eval(c->dev, 3, c->d_pods, c->d_ids, c->d_run, W, c->d_winsum, wbits, wmax,
-                                        x.ostride, nullptr, nullptr, nullptr, nullptr, 0, c->st, dext, x.tmax,
-                                        x.psoft, x.thist));
-          // sharded: over every shard's filtered nodes (the max, and the histogram of soft
-          // counts whose bin at the max the resolver's normalisation stop reads)
-          if (c->xchg && ((rc = allreduce_max_i32(c, x.tmax, x.tmax, W)) ||
-                          (rc = allreduce_sum_i32(c, x.thist, x.thist, W * KSG_TBINS))))
-            return rc;
-        }
-        HIPCHK(c, ksg_launch_win_eval(c->dev, anti ? 2 : 0, c->d_pods, c->d_ids, c->d_run, W, c->d_winsum, wbits,
-                                      wmax, x.ostride, c->d_dcnt,
-                                      (anti || esc || d1) ? reinterpret_cast<uint64_t*>(c->d_xsend + fit_off) : nullptr,
-                                      x.dmb, rr ? reinterpret_cast<uint64_t*>(c->d_xsend + x.b_off) : nullptr, x.dz,
-                                      c->st, dext, x.tmax, x.psoft));
-        if (evk) HIPCHK(c, hipEventRecord(c->wev[3 * k + 1], c->st));
-        if (c->xchg && (rc = allgather(c, c->d_xsend, c->d_xrecv, x.blk))) return rc;
-        if (plain) HIPCHK(c, ksg_launch_win_t0(full, W, c->d_run, x, c->st));
-        if (evk) HIPCHK(c, hipEventRecord(c->wev[3 * k + 2], c->st));
-        HIPCHK(c, ksg_launch_win_resolve(full, W, c->d_run, c->d_winsum, x, c->d_rng, c->d_out, c->st));
-        if (evk) HIPCHK(c, hipEventRecord(c->wev[3 * k + 3], c->st));
-      }
-      HIPCHK(c, hipMemcpyAsync(c->h_run, fused ? fruns + (K & 1) : c->d_run, sizeof(KsgWinRun), hipMemcpyDeviceToHost,
-                               c->st));
-      if ((rc = enqueue_tail())) return rc;
-      hphase(3);
-      if ((rc = overlap_work())) return rc;  // the host mirror catches up while the device works
-      if ((rc = wait_device(c))) return rc;
-      hphase(5);
-      const KsgWinRun r = *c->h_run;
-      if (r.windows > 0 && r.pos > pos) {  // pods per window, smoothed over rounds and batches
-        const double ppw = (double)(r.pos - pos) / (double)r.windows;
-        ppw_est = ppw_est > 0.0 ? 0.5 * ppw_est + 0.5 * ppw : ppw;
-        if (!c->xchg) c->ppw_est = ppw_est;
-      }
-      // the sampled launches (every one of the round's launches is a sampling
-      // candidate, including the ones after the batch was done, which return at
-      // once, so the mean matches a kernel trace of the run), scaled to all K
-      double ea = 0.0, eb = 0.0, et = 0.0;
-      uint32_t nt = 0;
-      for (uint32_t k = es ? (es - ev_off) % es : 0u; es && k < K; k += es) {
-        float a = 0.f, t0 = 0.f, b = 0.f;
-        if (fused) {  // (one kernel: its whole time is the resolver's, phase A runs inside it)
-          HIPCHK(c, hipEventElapsedTime(&b, c->wev[3 * k], c->wev[3 * k + 3]));
-        } else {
-          HIPCHK(c, hipEventElapsedTime(&a, c->wev[3 * k], c->wev[3 * k + 1]));
-          HIPCHK(c, hipEventElapsedTime(&t0, c->wev[3 * k + 1], c->wev[3 * k + 2]));
-          HIPCHK(c, hipEventElapsedTime(&b, c->wev[3 * k + 2], c->wev[3 * k + 3]));
-        }
-        ea += a;
-        et += t0;
-        eb += b;
-        ++nt;
-      }
-      if (nt) {
-        c->last_kms[0] += ea * K / nt;
-        c->last_kms[1] += eb * K / nt;
-        c->last_t0ms += et * K / nt;
-      }
-      c->last_kms[2] += K;
-      c->last_wsum += (double)W * K;
-      c->last_stats[0] += r.windows;
-      for (int q = 1; q <= 3; ++q) c->last_stats[q] += r.stops[q];
-      if (c->dbg_fail_next) {
-        c->dbg_fail_next = false;
-        return fail(c, KSG_ERR_STATE, "window resolver: injected failure (KSG_DEBUG & 16384) at pod %u", r.pos);
-      }
-      if (r.halt == KSG_HALT_HANG) return fail(c, KSG_ERR_STATE, "window resolver: ring wait timed out at pod %u", r.pos);
-      if (r.halt == KSG_HALT_BAD)
-        return fail(c, KSG_ERR_STATE,
-                    "window resolver: selection outside T0 at pod %u (inconsistent prefixes or drop positions: a bug, "
-                    "or stale verdicts under the KSG_DEBUG timing switches)", r.pos);
-      if (r.halt == KSG_HALT_BADCOUNT || r.pos < pos || r.pos > n)
-        return fail(c, KSG_ERR_STATE, "window resolver: bad progress (halt %u, pos %u -> %u)", r.halt, pos, r.pos);
-      pos = r.pos;
-      tail_queued = pos >= n && r.halt != KSG_HALT_OVERSIZE;  // (the copies saw the finished batch)
-      if (r.halt == KSG_HALT_OVERSIZE) {
-        // a pod whose id lists exceed the window record: the exact per-pod path
-        if (!c->xchg) {
-          HIPCHK(c, ksg_launch_batch(c->R, anti, c->dev, c->d_pods + pos, c->d_ids, 1, c->d_rng,
-                                     c->d_out + pos, c->st, dext ? dext + pos : nullptr));
-        } else {
-          if ((rc = scan_exchange(c, c->d_pods + pos, c->d_ids, KSG_MODE_BEGIN, nullptr, nullptr,
-                                  dext ? dext + pos : nullptr)))
-            return rc;
-          HIPCHK(c, ksg_launch_decide(c->dev, c->d_pods + pos, c->d_ids, rec_buf(c), c->rec_bytes, c->world,
-                                      c->d_shard_wlo, 1, 0, c->d_rng, c->d_out, pos, c->d_summary, c->st,
-                                      dext ? dext + pos : nullptr));
-        }
-        pos += 1;
-        ++c->last_stats[3];
-      }
-      // next round (rare: stops shortened this round's windows): the rest at W/2 pods per window
-      K = round_k(n - std::min(pos, n));
-      hphase(2);
-    }
-  } else if (!c->xchg) {
-    HIPCHK(c, ksg_launch_batch(c->R, anti_on(c), c->dev, c->d_pods, c->d_ids, n, c->d_rng, c->d_out, c->st, dext));
-  } else {
-    for (uint32_t i = 0; i < n; ++i) {
-      if ((rc = scan_exchange(c, c->d_pods + i, c->d_ids, KSG_MODE_BEGIN, nullptr, nullptr, dext ? dext + i : nullptr)))
-        return rc;
-      HIPCHK(c, ksg_launch_decide(c->dev, c->d_pods + i, c->d_ids, rec_buf(c), c->rec_bytes, c->world,
-                                  c->d_shard_wlo, 1, 0, c->d_rng, c->d_out, i, c->d_summary, c->st,
-                                  dext ? dext + i : nullptr));
-    }
-  }
-  if (!tail_queued) {
-    if ((rc = enqueue_tail())) return rc;
-    hphase(3);
-    if ((rc = overlap_work())) return rc;
-    if ((rc = wait_device(c))) return rc;
-    hphase(6);
-  }
-  memcpy(out_nodes, c->h_dn, (size_t)n * 4);
-  memcpy(rng_state, c->h_dn + dn_rng, 8);
-  float ms = 0.f;
-  HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->last_ms = ms;
-  // the device applied every commit; the host mirror replays them later
-  // (flush_deferred), overlapped with the next batch's device work
-  if (!stashed) {  // (overlap_work ran on every path that reaches here)
-    return fail(c, KSG_ERR_STATE, "internal: batch replay inputs missing");
-  }
-  guard.armed = false;
-  if (c->ext_on && !c->cur_ext)  // (plain entry point: the pods carry no extension requests)
-    for (uint32_t i = 0; i < n; ++i) c->ext_scalar.erase(pods[i].uid);
-  c->dfr_pods.swap(st_pods);
-  c->dfr_ids.swap(st_ids);
-  c->dfr_uids.swap(st_uids);
-  c->dfr_out.assign(out_nodes, out_nodes + n);
-  for (uint32_t i = 0; i < n; ++i)  // the uids of the pods that found no node are free again
-    if (out_nodes[i] < 0 && !dup_any) c->dfr_uids.erase(pods[i].uid);
-  if (dup_any) {  // a uid repeats within the batch: an error iff two placed pods share it
-    for (uint32_t i = 0; i < n; ++i) c->dfr_uids.erase(pods[i].uid);
-    for (uint32_t i = 0; i < n; ++i)
-      if (out_nodes[i] >= 0 && !c->dfr_uids.insert(pods[i].uid).second)  // (mirror_add reports it at the replay)
-        return fail(c, KSG_ERR_ARG, "pod %u: duplicate uid within the batch", i);
-  }
-  for (uint32_t i = 0; i < n; ++i) {
-    if (out_nodes[i] < 0) continue;
-    // (this batch's commits reach the mirror, and used_hi, at the next flush_deferred)
-    c->dfr_req += (uint64_t)std::max<int64_t>(std::max(pods[i].milli_cpu, pods[i].memory), 0);
-    if (pods[i].milli_cpu < 0 || pods[i].memory < 0) c->dfr_neg = true;
-    else c->dfr_sum = std::min<int64_t>(c->dfr_sum + std::min<int64_t>(std::min<int64_t>(pods[i].milli_cpu, KSG_WIN_LR_BOUND) +
-                                                                        std::min<int64_t>(pods[i].memory, KSG_WIN_LR_BOUND),
-                                                                        KSG_WIN_LR_BOUND), KSG_WIN_LR_BOUND + 1);
-  }
-  hphase(7);
-  double* t = c->totals;  // (layout: ksg_batch_totals in kschedgpu.h)
-  t[0] += 1;
-  t[1] += c->last_ms;
-  for (int q = 0; q < 3; ++q) t[2 + q] += c->last_kms[q];
-  t[17] += c->last_wsum;
-  t[18] += c->last_t0ms;
-  for (int q = 0; q < 4; ++q) t[5 + q] += c->last_stats[q];
-  for (int q = 0; q < 8; ++q) t[9 + q] += c->last_hus[q];
-  return KSG_OK;
-}
-
 int ksg_evaluate(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, uint8_t* fail_out, int64_t* score_out) {
   if (!c || !pod) return KSG_ERR_ARG;
   KSG_LOCK(c);
@@ -2562,42 +1673,6 @@ int ksg_set_allgather(ksg_ctx* c, ksg_allgather_fn fn, void* user) {
   return KSG_OK;
 }
 
-int ksg_set_window(ksg_ctx* c, uint32_t window) {
-  if (!c) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  c->window = window;
-  c->ppw_est = 0.0;
-  return KSG_OK;
-}
-
-int ksg_last_batch_stats(ksg_ctx* c, uint32_t* stats4) {
-  if (!c || !stats4) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  for (int i = 0; i < 4; ++i) stats4[i] = c->last_stats[i];
-  return KSG_OK;
-}
-
-int ksg_last_batch_kernel_ms(ksg_ctx* c, double* out3) {
-  if (!c || !out3) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  for (int i = 0; i < 3; ++i) out3[i] = c->last_kms[i];
-  return KSG_OK;
-}
-
-int ksg_batch_totals(ksg_ctx* c, double* out24) {
-  if (!c || !out24) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  for (int k = 0; k < 24; ++k) out24[k] = c->totals[k];
-  return KSG_OK;
-}
-
-int ksg_last_batch_host_us(ksg_ctx* c, double* out8) {
-  if (!c || !out8) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  for (int k = 0; k < 8; ++k) out8[k] = c->last_hus[k];
-  return KSG_OK;
-}
-
 int ksg_serve_stats(ksg_ctx* c, uint64_t* out4) {
   if (!c || !out4) return KSG_ERR_ARG;
   KSG_LOCK(c);
@@ -2618,13 +1693,6 @@ int ksg_debug_counters(ksg_ctx* c, int32_t* out, uint32_t n_words) {
   int32_t words[KSG_DEBUG_COUNTER_WORDS];
   HIPCHK(c, hipMemcpy(words, c->dev.dbgbuf, sizeof(words), hipMemcpyDeviceToHost));
   for (uint32_t k = 0; k < n_words; ++k) out[k] = k < KSG_DEBUG_COUNTER_WORDS ? words[k] : 0;
-  return KSG_OK;
-}
-
-int ksg_last_batch_ms(ksg_ctx* c, double* ms) {
-  if (!c || !ms) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  *ms = c->last_ms;
   return KSG_OK;
 }
 
@@ -2686,18 +1754,18 @@ static int admit_impl(ksg_ctx* c, int mode, const ksg_admission_set* sets, uint3
   const size_t o_pairs = o_ids + ((b_ids + 15) & ~(size_t)15), o_out = o_pairs + ((b_pairs + 15) & ~(size_t)15);
   const size_t total = o_out + n_pods;
   int rc;
-  if ((rc = grow(c, (void**)&c->d_admit, &c->admit_cap, total, 1))) return rc;
-  if ((rc = grow_host(c, &c->h_up, &c->h_up_cap, o_out))) return rc;
+  if ((rc = c->d_admit.grow(c, total))) return rc;
+  if ((rc = c->h_up.grow(c, o_out))) return rc;
   memcpy(c->h_up, sets, b_sets);
   memcpy(c->h_up + o_pods, pods, b_pods);
   if (b_ids) memcpy(c->h_up + o_ids, ids, b_ids);
   if (b_pairs) memcpy(c->h_up + o_pairs, pairs, b_pairs);
   HIPCHK(c, hipMemcpyAsync(c->d_admit, c->h_up, o_out, hipMemcpyHostToDevice, c->st));
-  HIPCHK(c, ksg_launch_admit(reinterpret_cast<const ksg_admission_set*>(c->d_admit), n_sets,
+  HIPCHK(c, ksg_launch_admit(reinterpret_cast<const ksg_admission_set*>(c->d_admit.p), n_sets,
                              reinterpret_cast<const ksg_pod*>(c->d_admit + o_pods),
                              reinterpret_cast<const uint32_t*>(c->d_admit + o_ids),
                              reinterpret_cast<const uint32_t*>(c->d_admit + o_pairs), mode, c->d_admit + o_out, c->st));
-  if ((rc = grow_host(c, &c->h_dn, &c->h_dn_cap, n_pods))) return rc;
+  if ((rc = c->h_dn.grow(c, n_pods))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->h_dn, c->d_admit + o_out, n_pods, hipMemcpyDeviceToHost, c->st));
   HIPCHK(c, hipStreamSynchronize(c->st));
   // pods outside every set keep KSG_ADMIT_OK; the kernel wrote the others
@@ -2776,12 +1844,12 @@ int ksg_read_ext_used(ksg_ctx* c, int64_t* used) {
 
 // validate a pod's extension record against the call's id array and record its
 // extended-resource requests by uid (the host mirror's AssumePod/remove)
-static int check_ext_range(ksg_ctx* c, const ksg_pod_ext* e, size_t n_ids) {
+int check_ext_range(ksg_ctx* c, const ksg_pod_ext* e, size_t n_ids) {
   if ((size_t)e->hard_off + e->n_hard > n_ids || (size_t)e->soft_off + e->n_soft > n_ids)
     return fail(c, KSG_ERR_ARG, "extension taint list out of range");
   return KSG_OK;
 }
-static int note_ext(ksg_ctx* c, const ksg_pod* p, const ksg_pod_ext* e, size_t n_ids) {
+int note_ext(ksg_ctx* c, const ksg_pod* p, const ksg_pod_ext* e, size_t n_ids) {
   if (int rc = check_ext_range(c, e, n_ids)) return rc;
   std::array<int64_t, KSG_MAX_SCALAR> sc{};
   bool any = false;
@@ -2807,7 +1875,7 @@ static bool has_repeat(const uint32_t* v, uint32_t n) {
   std::sort(s.begin(), s.end());
   return std::adjacent_find(s.begin(), s.end()) != s.end();
 }
-static int check_taint_ids(ksg_ctx* c, const ksg_pod_ext* e, const uint32_t* ids) {
+int check_taint_ids(ksg_ctx* c, const ksg_pod_ext* e, const uint32_t* ids) {
   for (uint32_t i = 0; i < e->n_hard; ++i)
     if (ids[e->hard_off + i] >= c->ext.max_taints) return fail(c, KSG_ERR_CAPACITY, "taint id out of range");
   for (uint32_t i = 0; i < e->n_soft; ++i)
@@ -2831,83 +1899,6 @@ int ksg_add_pod_ext(ksg_ctx* c, uint32_t host_id, const ksg_pod* pod, const ksg_
   c->cur_ext = ext;
   const int rc = ksg_add_pod(c, host_id, pod, ids);
   c->cur_ext = nullptr;
-  return rc;
-}
-
-int ksg_schedule_batch_draws(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint32_t* ids, uint32_t n_ids,
-                             const uint64_t* draws, uint32_t n_draws, uint32_t* draws_used, int32_t* out_nodes) {
-  if (!c || (n && (!pods || !out_nodes || !draws)) || !draws_used) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (n_draws < n) return fail(c, KSG_ERR_ARG, "%u draws for %u pods: one per pod that may find a node", n_draws, n);
-  for (uint32_t k = 0; k < n; ++k)
-    if (draws[k] > (uint64_t)INT64_MAX) return fail(c, KSG_ERR_ARG, "draw %u is not a rand.Int() value", k);
-  *draws_used = 0;
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
-  if (n == 0) return ksg_schedule_batch(c, pods, 0, ids, n_ids, &c->draw_tmp, out_nodes);
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rs_ = srv_stop(c)) return rs_;
-  if (int rc = grow(c, (void**)&c->d_draws, &c->draws_cap, n, sizeof(uint64_t))) return rc;
-  HIPCHK(c, hipMemcpy(c->d_draws, draws, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
-  c->dev.draws = c->d_draws;  // (the generator state is now the index of the next value)
-  uint64_t state = 0;
-  const int rc = ksg_schedule_batch(c, pods, n, ids, n_ids, &state, out_nodes);
-  c->dev.draws = nullptr;
-  if (rc == KSG_OK) *draws_used = (uint32_t)state;
-  return rc;
-}
-
-// A rejected Bind in batch mode (scheduler.go:107-112: no AssumePod for pod k, its rand.Int()
-// already drawn at generic_scheduler.go:94, pod k + 1 scheduled against the state without it).
-// The batch committed pods 0..n-1 in order, so undoing the commits of pods n-1 down to k leaves
-// exactly the state after pods 0..k-1; pods k+1..n-1 are then re-batched by the caller with the
-// draws they had consumed put back (a splitmix64 state is stepped back over them instead).
-int ksg_batch_unwind(ksg_ctx* c, const ksg_pod* pods, const int32_t* out_nodes, uint32_t n, uint32_t k,
-                     uint64_t* rng_state, uint32_t* draws_kept) {
-  if (!c || !pods || !out_nodes || !draws_kept || k >= n) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
-  if (out_nodes[k] < 0) return fail(c, KSG_ERR_ARG, "pod %u found no node: there was no Bind to reject", k);
-  if (int rs = cluster_ok(c)) return rs;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc0 = flush_deferred(c)) return rc0;  // (the batch's commits into the host mirror)
-  // (validate every uid before removing any: a failed call changes nothing)
-  for (uint32_t i = k; i < n; ++i)
-    if (out_nodes[i] >= 0 && !c->pods.count(pods[i].uid))
-      return fail(c, KSG_ERR_ARG, "pod %u (uid %llu) is not a committed pod of this context", i,
-                  (unsigned long long)pods[i].uid);
-  uint32_t kept = 0, back = 0;
-  for (uint32_t i = 0; i <= k; ++i) kept += out_nodes[i] >= 0 ? 1u : 0u;
-  for (uint32_t i = n; i-- > k;) {  // newest first
-    if (out_nodes[i] < 0) continue;
-    if (i > k) ++back;
-    if (int rc = remove_pod_impl(c, pods[i].uid)) return rc;
-  }
-  if (rng_state) *rng_state -= (uint64_t)back * ksg_rng_step(nullptr);
-  *draws_kept = kept;
-  return flush_patches(c);
-}
-
-int ksg_schedule_batch_ext(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
-                           uint32_t n_ids, uint64_t* rng_state, int32_t* out_nodes) {
-  if (!c || (n && (!pods || !out_nodes)) || !rng_state) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (ext && !c->ext_on) return fail(c, KSG_ERR_STATE, "extensions are off");
-  // validate the whole batch first; each placed pod's extended-resource requests
-  // are recorded (for the host mirror's deferred replay) only once the batch
-  // succeeded, and the pods that found no node leave no entry
-  if (c->ext_on && ext)
-    for (uint32_t i = 0; i < n; ++i) {
-      if (int rc = check_ext_range(c, ext + i, n_ids)) return rc;
-      if (int rc = check_taint_ids(c, ext + i, ids)) return rc;
-    }
-  c->cur_ext = ext;
-  const int rc = ksg_schedule_batch(c, pods, n, ids, n_ids, rng_state, out_nodes);
-  c->cur_ext = nullptr;
-  if (rc == KSG_OK && c->ext_on && ext)
-    for (uint32_t i = 0; i < n; ++i) {
-      if (out_nodes[i] >= 0) (void)note_ext(c, pods + i, ext + i, n_ids);
-      else c->ext_scalar.erase(pods[i].uid);
-    }
   return rc;
 }
 
@@ -2967,15 +1958,15 @@ int ksg_explain_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, u
   if ((rc = upload_pods(c, pods, n, ids, n_ids))) return rc;
   const ksg_pod_ext* dext = nullptr;
   if (ext) {  // (no record: node_fail skips the extension filters, as an all-zero record passes them)
-    if ((rc = grow(c, (void**)&c->d_pext, &c->pext_cap, n, sizeof(ksg_pod_ext)))) return rc;
+    if ((rc = c->d_pext.grow(c, n))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_pext, ext, (size_t)n * sizeof(ksg_pod_ext), hipMemcpyHostToDevice, c->st));
     dext = c->d_pext;
   }
   // hist and err for the whole call; the per-node codes in a bounded staging buffer, a chunk
   // of pods at a time (whole pod chunks of the kernel, at least one pod)
   const size_t hb = (size_t)n * KSG_EXPLAIN_SLOTS * sizeof(uint32_t);
-  if ((rc = grow(c, (void**)&c->d_xhist, &c->xhist_cap, hb + n, 1))) return rc;
-  uint32_t* d_hist = reinterpret_cast<uint32_t*>(c->d_xhist);
+  if ((rc = c->d_xhist.grow(c, hb + n))) return rc;
+  uint32_t* d_hist = reinterpret_cast<uint32_t*>(c->d_xhist.p);
   uint8_t* d_err = c->d_xhist + hb;
   HIPCHK(c, hipMemsetAsync(c->d_xhist, 0, hb + n, c->st));
   uint32_t per = 1u << 20;  // pods per launch (the grid's y extent stays far below 65,535)
@@ -2983,7 +1974,7 @@ int ksg_explain_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, u
     per = (uint32_t)std::min<size_t>(per, std::max<size_t>(kExplainStageBytes / c->N, 1));
     if (per > KSG_EXPLAIN_CHUNK) per -= per % KSG_EXPLAIN_CHUNK;
     per = std::min(per, n);
-    if ((rc = grow(c, (void**)&c->d_xcodes, &c->xcodes_cap, (size_t)per * c->N, 1))) return rc;
+    if ((rc = c->d_xcodes.grow(c, (size_t)per * c->N))) return rc;
   }
   if (!c->ev_x0) {
     HIPCHK(c, hipEventCreate(&c->ev_x0));

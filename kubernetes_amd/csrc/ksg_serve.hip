@@ -36,6 +36,7 @@
 
 #include "ksg_device.h"
 #include "ksg_exact.h"
+#include "ksg_launch.h"
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 

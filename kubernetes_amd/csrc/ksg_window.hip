@@ -47,6 +47,7 @@
 // whose service had commits earlier in the window is re-ranked per domain
 // (resolve2), or (LDS-slot resolver) ends the window.
 #include "ksg_device.h"
+#include "ksg_launch.h"
 #include "ksg_resolver.h"
 
 #include <algorithm>

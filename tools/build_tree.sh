@@ -2,6 +2,8 @@
 # build its libkschedgpu.so there (no UBSan twin, no oracle: its bench runs with
 # --no-cpu-baseline), so `cd _ab/<name> && python bench.py ...` runs that round's library
 # with that round's bench.py on the box next to the current tree's.
+# The sources are whatever that revision's csrc/ holds: every ksg_*.hip (ksg_plain_large.hip,
+# where there is one, under the max-ILP scheduler) and every *.cpp.
 # usage: tools/build_tree.sh <name> <REV>
 set -e
 cd "$(dirname "$0")/.."
@@ -12,19 +14,16 @@ git archive "$REV" | tar -x -C "$D"
 C=$D/kubernetes_amd/csrc
 mkdir -p "$C/_obj"
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-strict-aliasing -Wall -Wno-unused-function"
-pids=""
-for s in kernels window plain admit serve; do
-  hipcc $F -c "$C/ksg_$s.hip" -o "$C/_obj/ksg_$s.o" & pids="$pids $!"
+pids=""; objs=""
+for s in "$C"/ksg_*.hip "$C"/*.cpp; do
+  o=$C/_obj/$(basename "${s%.*}").o
+  X=""
+  case "$s" in */ksg_plain_large.hip) X="-mllvm -amdgpu-sched-strategy=max-ilp";; esac
+  hipcc $F $X -c "$s" -o "$o" & pids="$pids $!"
+  objs="$objs $o"
 done
-hipcc $F -c "$C/ksg_runtime.cpp" -o "$C/_obj/ksg_runtime.o" & pids="$pids $!"
-L=""
-if [ -f "$C/ksg_plain_large.hip" ]; then  # (round 6: the large-shard resolvers under the max-ILP scheduler)
-  hipcc $F -mllvm -amdgpu-sched-strategy=max-ilp -c "$C/ksg_plain_large.hip" -o "$C/_obj/ksg_plain_large.o" & pids="$pids $!"
-  L="$C/_obj/ksg_plain_large.o"
-fi
 for p in $pids; do wait $p; done
-hipcc --offload-arch=gfx950 -shared -fPIC $C/_obj/ksg_{kernels,window,plain,admit,serve}.o $L $C/_obj/ksg_runtime.o \
-  -o "$D/kubernetes_amd/libkschedgpu.so" -lrccl
+hipcc --offload-arch=gfx950 -shared -fPIC $objs -o "$D/kubernetes_amd/libkschedgpu.so" -lrccl
 rm -rf "$C/_obj"
 # (its tests and docs are not needed on the box)
 rm -rf "$D/tests" "$D/profiles" "$D"/*.md "$D"/*_r0*.json
