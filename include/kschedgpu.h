@@ -567,6 +567,57 @@ int ksg_explain_batch(ksg_ctx* ctx, const ksg_pod* pods, const ksg_pod_ext* ext 
  * on the context's stream (the copies out are not in it). Diagnostics. */
 int ksg_last_explain_ms(ksg_ctx* ctx, double* ms);
 
+/* ---- Ranked hosts for many pods (prioritizeNodes + the sorted HostPriorityList) ----
+ * One device pass filters and scores n pods against every node, as ksg_evaluate does
+ * for one (generic_scheduler.go:84-96, 136-177), and returns per pod i, against the
+ * state AT THE TIME OF THE CALL (as ksg_explain_batch words it):
+ *   fit_count[i]: the nodes with fail code 0 (ksg_explain_batch's hist[i][0]).
+ *   max_score[i], tie_count[i]: what ksg_schedule_begin would return for the pod now:
+ *     the best combined score (Go int: wrapping) and the fitting nodes at it. 0, 0 when
+ *     nothing fits, and 0, 0 when the config has priority configs whose weights are all 0
+ *     (the empty HostPriorityList; fit_count may still be non-zero). Without priority
+ *     configs (EqualPriority fallback) every fitting node scores 1.
+ *   top_nodes[i * top + j], top_scores[i * top + j]: entry j of the HostPriorityList in
+ *     the reference's order, score descending then node rank descending (types.go:42-47).
+ *     L = min(top, fit_count[i]) entries are listed (L = 0 for the empty list above);
+ *     the first min(top, tie_count[i]) are the nodes ksg_schedule_commit(tie_index = j)
+ *     would pick. Entries j >= L are -1 / 0.
+ *   scores (optional, n * n_nodes): scores[i * n_nodes + node] = the combined score
+ *     where the pod fits, KSG_SCORE_NOFIT elsewhere: bit-identical to ksg_evaluate's
+ *     score_out row of that pod. NULL: no per-node values are produced or copied.
+ *   err (n): 1 for a pod whose ServiceAffinity peer is on a host that is not a known
+ *     node (predicates.go:293-296). Its max_score, tie_count and fit_count are 0, its top
+ *     entries -1 / 0 and its scores row all KSG_SCORE_NOFIT; the other pods are unaffected.
+ * Scores are always computed as wrapping int64 (the int32 kernels are proven equal to
+ * that while a context is narrow), so unlike ksg_evaluate the call does not look at the
+ * pods' requests to choose between the int32 and the int64 kernels and leaves the path
+ * later batches take as it was.
+ * ext (optional, extension contexts): ext[i] goes with pods[i]; NULL = all-zero records.
+ * Every node of the cluster is covered on every rank of a sharded context (node state is
+ * replicated; ServiceAntiAffinity's domain counts and TaintToleration's max are taken
+ * over all nodes), with no exchange: ranks need not make the call together.
+ * uid is ignored. n == 0: KSG_OK, nothing written. KSG_ERR_ARG for max_score, tie_count,
+ * fit_count or err NULL with n > 0, for top > KSG_PRIO_MAX_TOP, and for top > 0 with
+ * top_nodes or top_scores NULL (both may be NULL iff top == 0). KSG_ERR_STATE while a
+ * ksg_schedule_begin is pending, or for ext on a context without extensions; KSG_NONODES
+ * for an empty node list. On any of these nothing is written. Pods and id extents are
+ * validated as by ksg_schedule_batch, extension records as by ksg_schedule_batch_ext.
+ * The call changes nothing a later call can observe: not the committed totals, the
+ * generator state, the uid bookkeeping, the extended-resource usage or the results or
+ * path of any later batch. The pods are processed in chunks whose per-node scores and
+ * per-tile partial results each fit a fixed device staging budget (64 MiB). */
+#define KSG_PRIO_MAX_TOP 16
+#define KSG_SCORE_NOFIT (-0x7fffffffffffffffLL - 1)  /* what ksg_evaluate's score_out holds where a node does not fit */
+int ksg_prioritize_batch(ksg_ctx* ctx, const ksg_pod* pods, const ksg_pod_ext* ext /* NULL: all-zero records */,
+                         uint32_t n, const uint32_t* ids, uint32_t n_ids, uint32_t top /* 0..KSG_PRIO_MAX_TOP */,
+                         int64_t* max_score /* n */, uint32_t* tie_count /* n */, uint32_t* fit_count /* n */,
+                         int32_t* top_nodes /* n * top; may be NULL iff top == 0 */,
+                         int64_t* top_scores /* n * top; may be NULL iff top == 0 */,
+                         int64_t* scores /* optional, n * n_nodes */, uint8_t* err /* n */);
+/* Device time (ms) of the last ksg_prioritize_batch's kernel launches, from HIP events
+ * on the context's stream (the copies out are not in it). Diagnostics. */
+int ksg_last_prioritize_ms(ksg_ctx* ctx, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

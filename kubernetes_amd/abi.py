@@ -52,6 +52,8 @@ FAIL_TAINTS = 8
 FAIL_SCALAR = 9
 MAX_SCALAR = 4
 EXPLAIN_SLOTS = 16  # ksg_explain_batch: histogram slots per pod (fail codes 0..9 used)
+PRIO_MAX_TOP = 16  # ksg_prioritize_batch: the longest HostPriorityList head per pod
+SCORE_NOFIT = -(1 << 63)  # ... and ksg_evaluate: the score of a node the pod does not fit
 
 MAX_ANTI = 64
 MAX_LABEL_PREF = 32
@@ -220,6 +222,8 @@ EXPORTS = [
     "ksg_evaluate_ext",
     "ksg_explain_batch",
     "ksg_last_explain_ms",
+    "ksg_prioritize_batch",
+    "ksg_last_prioritize_ms",
 ]
 
 # int (*ksg_allgather_fn)(void* user, const void* send, void* recv, uint64_t bytes)
@@ -293,6 +297,10 @@ def load_library() -> C.CDLL:
         # (ctx, pods, ext | NULL, n, ids, n_ids, codes | NULL, hist, err)
         "ksg_explain_batch": (C.c_int, [vp, vp, vp, U32, vp, U32, vp, vp, vp]),
         "ksg_last_explain_ms": (C.c_int, [vp, P(C.c_double)]),
+        # (ctx, pods, ext | NULL, n, ids, n_ids, top, max_score, tie_count, fit_count, top_nodes | NULL,
+        #  top_scores | NULL, scores | NULL, err)
+        "ksg_prioritize_batch": (C.c_int, [vp, vp, vp, U32, vp, U32, U32, vp, vp, vp, vp, vp, vp, vp]),
+        "ksg_last_prioritize_ms": (C.c_int, [vp, P(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

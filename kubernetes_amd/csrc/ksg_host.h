@@ -199,6 +199,12 @@ struct ksg_ctx {
   DevBuf<uint8_t> d_xcodes, d_xhist;
   hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr;  // around its kernel launches
   double last_explain_ms = 0.0;
+  // ksg_prioritize_batch, per chunk of pods (each bounded by kExplainStageBytes): the per-node
+  // scores; the normalised terms int32[per][D + 1], the tile partials and their candidates
+  // (one buffer); and for the whole call the per-pod results (one buffer, one copy out)
+  DevBuf<int64_t> d_pscores;
+  DevBuf<uint8_t> d_ppart, d_pout;
+  double last_prioritize_ms = 0.0;
   std::vector<KsgPatch> patches;
 
   // host mirror

@@ -262,6 +262,17 @@ typedef ksg_shard_record KsgRecordHdr;  // public layout (include/kschedgpu.h)
 #define KSG_EXPLAIN_TILE 256
 #define KSG_EXPLAIN_CHUNK 32
 
+// ksg_prioritize_batch (ksg_prioritize.hip) keeps that tiling. Per (pod, node tile) the score
+// pass leaves one KsgPrioPart and the tile's best `top` entries (scores int64, nodes int32;
+// node -1 past the tile's fitting nodes); the merge pass reads them, one wave per pod.
+#define KSG_PRIO_WAVES (KSG_EXPLAIN_TILE / 64)
+struct KsgPrioPart {
+  int64_t max;    // best combined score of the tile's fitting nodes (unread when fit == 0)
+  uint32_t cnt;   // fitting nodes at it
+  uint32_t fit;   // fitting nodes
+};
+static_assert(sizeof(KsgPrioPart) == 16, "KsgPrioPart layout");
+
 // ksg_admit_kernel modes (ksg_admit.hip)
 #define KSG_ADMIT_MODE_CAPACITY 1
 #define KSG_ADMIT_MODE_SELECTOR 2

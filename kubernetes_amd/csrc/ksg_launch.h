@@ -64,4 +64,18 @@ hipError_t ksg_launch_admit(const ksg_admission_set* sets, uint32_t n_sets, cons
 hipError_t ksg_launch_explain(const KsgDev& d, const ksg_pod* pods, const ksg_pod_ext* exts, const uint32_t* ids,
                               uint32_t n_pods, uint8_t* codes, uint32_t* hist, uint8_t* err, hipStream_t st);
 
+// ksg_prioritize.hip (all per-pod arrays are indexed from `pods`; dnorm = int32[n_pods][D + 1]:
+// a pod's ServiceAntiAffinity domain counts, then its TaintToleration max)
+bool ksg_prio_needs_reduce(const KsgDev& d, bool have_ext);
+hipError_t ksg_launch_prio_reduce(const KsgDev& d, const ksg_pod* pods, const ksg_pod_ext* exts, const uint32_t* ids,
+                                  uint32_t n_pods, int32_t* dnorm, hipStream_t st);
+hipError_t ksg_launch_prio_score(const KsgDev& d, const ksg_pod* pods, const ksg_pod_ext* exts, const uint32_t* ids,
+                                 uint32_t n_pods, uint32_t top, const int32_t* dnorm, int64_t* scores,
+                                 KsgPrioPart* part, int64_t* cand_score, int32_t* cand_node, uint8_t* err,
+                                 hipStream_t st);
+hipError_t ksg_launch_prio_merge(const KsgDev& d, uint32_t n_pods, uint32_t top, const KsgPrioPart* part,
+                                 const int64_t* cand_score, const int32_t* cand_node, int64_t* max_score,
+                                 uint32_t* tie_count, uint32_t* fit_count, int32_t* top_nodes, int64_t* top_scores,
+                                 hipStream_t st);
+
 #endif  // KSG_LAUNCH_H_

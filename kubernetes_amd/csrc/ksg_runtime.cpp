@@ -2007,6 +2007,108 @@ int ksg_last_explain_ms(ksg_ctx* c, double* ms) {
   return KSG_OK;
 }
 
+// Ranked hosts for many pods: the grid-wide reduce / score / merge passes of ksg_prioritize.hip
+// over the device state as it stands. Protocol and validation are ksg_explain_batch's. Scores
+// are always wrapping int64, so note_requests is NOT called and later batches take the path
+// they would have taken. A sharded context covers the whole (replicated) cluster alone.
+int ksg_prioritize_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
+                         uint32_t n_ids, uint32_t top, int64_t* max_score, uint32_t* tie_count, uint32_t* fit_count,
+                         int32_t* top_nodes, int64_t* top_scores, int64_t* scores, uint8_t* err) {
+  if (!c || (n && (!pods || !max_score || !tie_count || !fit_count || !err))) return KSG_ERR_ARG;
+  KSG_LOCK(c);
+  if (top > KSG_PRIO_MAX_TOP) return fail(c, KSG_ERR_ARG, "top %u > KSG_PRIO_MAX_TOP", top);
+  if (n && top && (!top_nodes || !top_scores)) return fail(c, KSG_ERR_ARG, "top > 0 needs top_nodes and top_scores");
+  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
+  if (ext && !c->ext_on) return fail(c, KSG_ERR_STATE, "extensions are off");
+  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
+  if (int rc0 = flush_deferred(c)) return rc0;
+  if (int rs = cluster_ok(c)) return rs;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->last_prioritize_ms = 0.0;
+  if (n == 0) return KSG_OK;
+  if (c->N == 0) return KSG_NONODES;
+  if (n_ids && !ids) return fail(c, KSG_ERR_ARG, "ids missing");
+  int rc;
+  for (uint32_t i = 0; i < n; ++i) {
+    if ((rc = check_pod(c, pods + i, ids, n_ids))) return rc;
+    if (ext && ((rc = check_ext_range(c, ext + i, n_ids)) || (rc = check_taint_ids(c, ext + i, ids)))) return rc;
+  }
+  if ((rc = flush_patches(c))) return rc;
+  if ((rc = upload_pods(c, pods, n, ids, n_ids))) return rc;
+  const ksg_pod_ext* dext = nullptr;
+  if (c->ext_on) {  // (no records: all-zero ones, which is what ksg_evaluate scores a plain pod with)
+    if ((rc = c->d_pext.grow(c, n))) return rc;
+    if (ext) HIPCHK(c, hipMemcpyAsync(c->d_pext, ext, (size_t)n * sizeof(ksg_pod_ext), hipMemcpyHostToDevice, c->st));
+    else HIPCHK(c, hipMemsetAsync(c->d_pext, 0, (size_t)n * sizeof(ksg_pod_ext), c->st));
+    dext = c->d_pext;
+  }
+  // the per-pod results of the whole call: int64 max[n], int64 top_scores[n][top], uint32 ties[n],
+  // uint32 fit[n], int32 top_nodes[n][top], uint8 err[n]
+  const size_t o_ts = (size_t)n * 8, o_tie = o_ts + (size_t)n * top * 8, o_fit = o_tie + (size_t)n * 4;
+  const size_t o_tn = o_fit + (size_t)n * 4, o_err = o_tn + (size_t)n * top * 4, ob = o_err + n;
+  if ((rc = c->d_pout.grow(c, ob)) || (rc = c->h_dn.grow(c, ob))) return rc;
+  uint8_t* const po = c->d_pout;
+  // pods per launch: the normalised terms, tile partials and candidates of a chunk, and its
+  // per-node scores, each within the staging budget (whole pod chunks of the kernels, >= 1 pod)
+  const size_t T = (c->nw + KSG_PRIO_WAVES - 1) / KSG_PRIO_WAVES, D1 = (size_t)c->dev.n_domains_total + 1;
+  const size_t bpp = D1 * 4 + T * (sizeof(KsgPrioPart) + (size_t)top * 12);
+  uint32_t per = (uint32_t)std::min<size_t>(1u << 20, std::max<size_t>(kExplainStageBytes / bpp, 1));
+  if (scores) per = (uint32_t)std::min<size_t>(per, std::max<size_t>(kExplainStageBytes / ((size_t)c->N * 8), 1));
+  if (per > KSG_EXPLAIN_CHUNK) per -= per % KSG_EXPLAIN_CHUNK;
+  per = std::min(per, n);
+  const size_t o_part = ((size_t)per * D1 * 4 + 15) & ~(size_t)15, o_cs = o_part + (size_t)per * T * sizeof(KsgPrioPart);
+  const size_t o_cn = o_cs + (size_t)per * T * top * 8;
+  if ((rc = c->d_ppart.grow(c, o_cn + (size_t)per * T * top * 4))) return rc;
+  if (scores && (rc = c->d_pscores.grow(c, (size_t)per * c->N))) return rc;
+  int32_t* const dnorm = reinterpret_cast<int32_t*>(c->d_ppart.p);
+  KsgPrioPart* const part = reinterpret_cast<KsgPrioPart*>(c->d_ppart + o_part);
+  int64_t* const cs = reinterpret_cast<int64_t*>(c->d_ppart + o_cs);
+  int32_t* const cn = reinterpret_cast<int32_t*>(c->d_ppart + o_cn);
+  const bool reduce = ksg_prio_needs_reduce(c->dev, ext != nullptr);
+  if (!c->ev_x0) {
+    HIPCHK(c, hipEventCreate(&c->ev_x0));
+    HIPCHK(c, hipEventCreate(&c->ev_x1));
+  }
+  for (uint32_t a = 0; a < n; a += per) {
+    const uint32_t m = std::min(per, n - a);
+    const ksg_pod_ext* xa = dext ? dext + a : nullptr;
+    HIPCHK(c, hipEventRecord(c->ev_x0, c->st));
+    HIPCHK(c, hipMemsetAsync(dnorm, 0, (size_t)m * D1 * 4, c->st));
+    if (reduce) HIPCHK(c, ksg_launch_prio_reduce(c->dev, c->d_pods + a, xa, c->d_ids, m, dnorm, c->st));
+    HIPCHK(c, ksg_launch_prio_score(c->dev, c->d_pods + a, xa, c->d_ids, m, top, dnorm, scores ? c->d_pscores.p : nullptr,
+                                    part, cs, cn, po + o_err + a, c->st));
+    HIPCHK(c, ksg_launch_prio_merge(c->dev, m, top, part, cs, cn, reinterpret_cast<int64_t*>(po) + a,
+                                    reinterpret_cast<uint32_t*>(po + o_tie) + a, reinterpret_cast<uint32_t*>(po + o_fit) + a,
+                                    reinterpret_cast<int32_t*>(po + o_tn) + (size_t)a * top,
+                                    reinterpret_cast<int64_t*>(po + o_ts) + (size_t)a * top, c->st));
+    HIPCHK(c, hipEventRecord(c->ev_x1, c->st));
+    if (scores)
+      HIPCHK(c, hipMemcpyAsync(scores + (size_t)a * c->N, c->d_pscores, (size_t)m * c->N * 8, hipMemcpyDeviceToHost, c->st));
+    if (a + per >= n)  // the last chunk's wait also brings the per-pod results back
+      HIPCHK(c, hipMemcpyAsync(c->h_dn, po, ob, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));  // (the staging buffers are reused by the next chunk)
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_x0, c->ev_x1));
+    c->last_prioritize_ms += ms;
+  }
+  memcpy(max_score, c->h_dn, (size_t)n * 8);
+  memcpy(tie_count, c->h_dn + o_tie, (size_t)n * 4);
+  memcpy(fit_count, c->h_dn + o_fit, (size_t)n * 4);
+  if (top) {
+    memcpy(top_scores, c->h_dn + o_ts, (size_t)n * top * 8);
+    memcpy(top_nodes, c->h_dn + o_tn, (size_t)n * top * 4);
+  }
+  memcpy(err, c->h_dn + o_err, n);
+  return KSG_OK;
+}
+
+int ksg_last_prioritize_ms(ksg_ctx* c, double* ms) {
+  if (!c || !ms) return KSG_ERR_ARG;
+  KSG_LOCK(c);
+  *ms = c->last_prioritize_ms;
+  return KSG_OK;
+}
+
 int ksg_check_pods_exceeding_capacity(ksg_ctx* c, const ksg_admission_set* sets, uint32_t n_sets,
                                       const ksg_pod* pods, uint32_t n_pods, uint8_t* fits) {
   const int rc = admit_impl(c, KSG_ADMIT_MODE_CAPACITY, sets, n_sets, pods, n_pods, nullptr, 0, nullptr, 0, fits);

@@ -300,6 +300,40 @@ class DeviceScheduler:
         self._lib.ksg_last_explain_ms(self._ctx, C.byref(ms))
         return ms.value
 
+    def prioritize(self, batch: PodBatch, top: int = 0, want_scores: bool = False):
+        """ksg_prioritize_batch: filter and score every pod of `batch` against every node of the
+        cluster as it stands, in one device pass, committing nothing.
+        -> (max_score int64[n], tie_count uint32[n], fit_count uint32[n], top_nodes int32[n, top],
+        top_scores int64[n, top], scores int64[n, N] | None, err uint8[n]): what begin() would
+        return for each pod now, the nodes it fits, the head of its HostPriorityList (score
+        descending, then node rank descending; -1 / 0 past min(top, fit_count)), the per-node
+        combined scores (want_scores; abi.SCORE_NOFIT where the pod does not fit), and 1 where
+        the pod's ServiceAffinity peer is on an unknown host (its row: 0, 0, 0, -1 / 0, NOFIT)."""
+        n = len(batch)
+        pods = np.ascontiguousarray(batch.pods, dtype=abi.POD_DTYPE)
+        ids = _u32(batch.ids if len(batch.ids) else np.zeros(1, np.uint32))
+        ext = None if batch.ext is None else np.ascontiguousarray(batch.ext, dtype=abi.POD_EXT_DTYPE)
+        mx = np.zeros(n, np.int64)
+        ties = np.zeros(n, np.uint32)
+        fit = np.zeros(n, np.uint32)
+        tn = np.full((n, top), -1, np.int32)
+        ts = np.zeros((n, top), np.int64)
+        scores = np.full((n, self.n_nodes), abi.SCORE_NOFIT, np.int64) if want_scores else None
+        err = np.zeros(n, np.uint8)
+        rc = self._lib.ksg_prioritize_batch(self._ctx, abi.ptr(pods), abi.ptr(ext), n, abi.ptr(ids), len(batch.ids),
+                                            int(top), abi.ptr(mx), abi.ptr(ties), abi.ptr(fit),
+                                            abi.ptr(tn) if tn.size else None, abi.ptr(ts) if ts.size else None,
+                                            abi.ptr(scores) if want_scores and scores.size else None, abi.ptr(err))
+        if rc not in (abi.KSG_OK, abi.KSG_NONODES):
+            self._err(rc)
+        return mx, ties, fit, tn, ts, scores, err
+
+    def last_prioritize_ms(self) -> float:
+        """Device ms of the last prioritize()'s kernel launches (HIP events)."""
+        ms = C.c_double(0)
+        self._lib.ksg_last_prioritize_ms(self._ctx, C.byref(ms))
+        return ms.value
+
     def set_window(self, window: int):
         """Pods per speculative window (0 = exact one-pod-at-a-time kernel)."""
         rc = self._lib.ksg_set_window(self._ctx, int(window))

@@ -305,6 +305,34 @@ class GPUScheduler:
             errors[i] = FitError(pods[i], failed, counts)
         return errors
 
+    # ---- dry run: the sorted HostPriorityList's head ---------------------------------
+    def prioritize(self, pods: Sequence[Pod], minion_lister, top: int = 3) -> list:
+        """Where would each pod go now, and how close is the runner-up: per pod the first `top`
+        entries (host name, score) of the HostPriorityList selectHost would read, in its order
+        (score descending, then host descending; generic_scheduler.go:84-96, types.go:42-47),
+        from one ksg_prioritize_batch. Nothing is committed or drawn, and no pod is assumed. An
+        empty list: nothing fits, or the priority list is empty (Schedule's FitError). A
+        SchedulingError instead of a list: the pod's ServiceAffinity peer is on an unknown host;
+        NoMinionsError entries without nodes."""
+        nodes = minion_lister.list()
+        if len(nodes) == 0:
+            return [NoMinionsError() for _ in pods]
+        self._sync(nodes)
+        if not pods:
+            return []
+        b = PodBatchBuilder(self.view, self.aff_labels)
+        for p in pods:
+            b.add(p, 0)  # (the call ignores uids)
+        _, _, _, tn, ts, _, err = self.engine.prioritize(b.build(), top=top)
+        names = self.view.names
+        out: list = []
+        for i in range(len(pods)):
+            if err[i]:
+                out.append(SchedulingError("service affinity peer is not on a known node"))
+            else:
+                out.append([(names[int(n)], int(s)) for n, s in zip(tn[i], ts[i]) if n >= 0])
+        return out
+
 
 def new_gpu_scheduler(config: SchedulerConfig, pod_lister, service_lister=None, random=None,
                       device: int = 0) -> GPUScheduler:
