@@ -618,6 +618,81 @@ int ksg_prioritize_batch(ksg_ctx* ctx, const ksg_pod* pods, const ksg_pod_ext* e
  * on the context's stream (the copies out are not in it). Diagnostics. */
 int ksg_last_prioritize_ms(ksg_ctx* ctx, double* ms);
 
+/* ---- Headroom for many pods: how many copies of a pod each node can take ----
+ * The gang-admission and capacity-planning question ("do 64 replicas of this pod fit now",
+ * "how many more can the cluster hold, and what runs out first"), answered in one device
+ * pass without committing anything. For pod i and node n, against the state AT THE TIME OF
+ * THE CALL, the count is the largest k <= limit such that for every j < k the node's fail
+ * code for the pod (what ksg_evaluate reports) is 0 once j copies of the pod (distinct uids,
+ * otherwise identical) have been added to node n by ksg_add_pod. Copies on other nodes are
+ * not part of the definition. The count is > 0 exactly where ksg_explain_batch's code is 0.
+ * The predicates of this reference are per-node monotone in the number of copies, so the
+ * count is min(limit, the bounds that apply), with, in the fail-code order:
+ *   disk    NoDiskConflict is on and the pod has a GCE PD: 1 (the second copy conflicts).
+ *   ports   PodFitsPorts is on and the pod has a host port: 1.
+ *   cpu     PodFitsResources is on, the pod is not the zero-request pod, the node's
+ *           cap_milli_cpu != 0 and milli_cpu > 0: floor((cap - used) / milli_cpu), with the
+ *           reference's wrapping subtraction; exact for every int64 capacity and total.
+ *   memory  the same with cap_memory and memory.
+ *   scalar r (r < n_scalar)  KSG_EXT_SCALAR is on, a record is given and scalar[r] > 0:
+ *           floor(((uint64)cap - (uint64)used) / scalar[r]); exact wherever used + scalar[r]
+ *           does not overflow int64. Where it does, the count and binding of that (node,
+ *           resource) are unspecified (the node still counts as fitting).
+ * HostName, LabelsPresence and the static terms, MatchNodeSelector, ServiceAffinity and the
+ * taints do not change with copies on the node. Outputs, per pod i:
+ *   total[i]      sum of the counts over the nodes. total[i] >= r answers "does a gang of r
+ *                 fit", exactly whenever the nodes are independent. They are not in ONE case:
+ *                 a ServiceAffinity predicate while the pod's service has no peer yet. The
+ *                 first copy placed becomes the peer, and copies on other nodes must then
+ *                 share its affinity labels, so there total[i] is an upper bound.
+ *   fit_count[i]  nodes with count > 0.   max_count[i]  the largest count.
+ *   bind_hist (n * KSG_HEADROOM_SLOTS): bind_hist[i][b] = nodes whose binding is b; a row
+ *     sums to n_nodes. The binding of a node is KSG_ROOM_NONE if its count is 0, else the
+ *     first constraint in the order above whose bound equals the count (for count < limit:
+ *     the refinement of the fail code the node reports once it holds that many copies), or
+ *     KSG_ROOM_LIMIT if none does (then count == limit and nothing binds below it).
+ *   counts (optional, n * n_nodes): counts[i * n_nodes + node]. NULL: no per-node values are
+ *     produced or copied.
+ *   err (n): KSG_HEADROOM_ERR_PEER for a pod whose ServiceAffinity peer is on a host that is
+ *     not a known node (as ksg_explain_batch reports it), KSG_HEADROOM_ERR_NEGATIVE for a
+ *     pod with a negative milli_cpu, memory or scalar[r < n_scalar] (legal elsewhere, but the
+ *     count is then not monotone; PEER is reported first). An error row has total, fit_count,
+ *     max_count, its bind_hist row and its counts row all zero; the other pods are unaffected.
+ * ext (optional, extension contexts): ext[i] goes with pods[i]; NULL skips the extension
+ * filters, as an all-zero record passes them.
+ * Every node of the cluster is covered on every rank of a sharded context (node state is
+ * replicated), with no exchange: ranks need not make the call together.
+ * uid is ignored: a pod whose uid is committed, or the same pod twice, is legal.
+ * n == 0: KSG_OK, nothing written. KSG_ERR_ARG for total, fit_count, max_count, bind_hist or
+ * err NULL with n > 0, and for limit == 0. KSG_ERR_STATE while a ksg_schedule_begin is
+ * pending, or for ext on a context without extensions; KSG_NONODES for an empty node list.
+ * On any of these nothing is written. Pods and id extents are validated as by
+ * ksg_schedule_batch, extension records as by ksg_schedule_batch_ext.
+ * The call changes nothing a later call can observe: not the committed totals, the
+ * generator state, the uid bookkeeping, the extended-resource usage or the results or path
+ * of any later batch (it computes no score and does not look at the pods' requests to choose
+ * between the int32 and the int64 kernels). The pods are processed in chunks whose per-node
+ * counts fit a fixed device staging budget (64 MiB; KSG_HEADROOM_STAGE_BYTES in the
+ * environment at ksg_create overrides it: a test knob). */
+#define KSG_HEADROOM_SLOTS 16
+#define KSG_ROOM_NONE 0
+#define KSG_ROOM_LIMIT 1
+#define KSG_ROOM_DISK 2
+#define KSG_ROOM_PORTS 3
+#define KSG_ROOM_CPU 4
+#define KSG_ROOM_MEMORY 5
+#define KSG_ROOM_SCALAR0 6      /* + r, r < KSG_MAX_SCALAR */
+#define KSG_HEADROOM_ERR_PEER 1
+#define KSG_HEADROOM_ERR_NEGATIVE 2
+int ksg_headroom_batch(ksg_ctx* ctx, const ksg_pod* pods, const ksg_pod_ext* ext /* NULL: all-zero */,
+                       uint32_t n, const uint32_t* ids, uint32_t n_ids, uint32_t limit /* >= 1 */,
+                       uint64_t* total /* n: sum of counts */, uint32_t* fit_count /* n: nodes with count > 0 */,
+                       uint32_t* max_count /* n */, uint32_t* bind_hist /* n * KSG_HEADROOM_SLOTS */,
+                       uint32_t* counts /* optional, n * n_nodes */, uint8_t* err /* n */);
+/* Device time (ms) of the last ksg_headroom_batch's kernel launches, from HIP events
+ * on the context's stream (the copies out are not in it). Diagnostics. */
+int ksg_last_headroom_ms(ksg_ctx* ctx, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

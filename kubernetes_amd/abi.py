@@ -54,6 +54,16 @@ MAX_SCALAR = 4
 EXPLAIN_SLOTS = 16  # ksg_explain_batch: histogram slots per pod (fail codes 0..9 used)
 PRIO_MAX_TOP = 16  # ksg_prioritize_batch: the longest HostPriorityList head per pod
 SCORE_NOFIT = -(1 << 63)  # ... and ksg_evaluate: the score of a node the pod does not fit
+HEADROOM_SLOTS = 16  # ksg_headroom_batch: histogram slots per pod (bindings ROOM_* 0..9 used)
+ROOM_NONE = 0
+ROOM_LIMIT = 1
+ROOM_DISK = 2
+ROOM_PORTS = 3
+ROOM_CPU = 4
+ROOM_MEMORY = 5
+ROOM_SCALAR0 = 6  # + r, r < MAX_SCALAR
+HEADROOM_ERR_PEER = 1
+HEADROOM_ERR_NEGATIVE = 2
 
 MAX_ANTI = 64
 MAX_LABEL_PREF = 32
@@ -224,6 +234,8 @@ EXPORTS = [
     "ksg_last_explain_ms",
     "ksg_prioritize_batch",
     "ksg_last_prioritize_ms",
+    "ksg_headroom_batch",
+    "ksg_last_headroom_ms",
 ]
 
 # int (*ksg_allgather_fn)(void* user, const void* send, void* recv, uint64_t bytes)
@@ -301,6 +313,9 @@ def load_library() -> C.CDLL:
         #  top_scores | NULL, scores | NULL, err)
         "ksg_prioritize_batch": (C.c_int, [vp, vp, vp, U32, vp, U32, U32, vp, vp, vp, vp, vp, vp, vp]),
         "ksg_last_prioritize_ms": (C.c_int, [vp, P(C.c_double)]),
+        # (ctx, pods, ext | NULL, n, ids, n_ids, limit, total, fit_count, max_count, bind_hist, counts | NULL, err)
+        "ksg_headroom_batch": (C.c_int, [vp, vp, vp, U32, vp, U32, U32, vp, vp, vp, vp, vp, vp]),
+        "ksg_last_headroom_ms": (C.c_int, [vp, P(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

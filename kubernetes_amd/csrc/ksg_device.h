@@ -380,6 +380,90 @@ __device__ __forceinline__ int node_fail_l(const KsgDev& d, const PodCtx& c, con
   return KSG_FAIL_NONE;
 }
 
+// min(floor(a / b), cap) for 0 < b < 2^63 and cap <= 2^32, exact for every a < 2^64
+// (ksg_headroom_batch's quotients; gfx950 has no 64-bit integer divide instruction).
+//   DIV 0: the compiler's expansion of the 64-bit divide.
+//   DIV 1: e = (double)a * (1.0 / (double)b), every step correctly rounded, so
+//     |e - a/b| <= e * 2^-50. e >= cap + 2 proves a/b > cap. Otherwise e < 2^32 + 2 is within
+//     2^-17 of a/b, trunc(e) is within one of the quotient, and from trunc(e) - 1 (never above
+//     it, so q * b <= a cannot wrap) at most two exact compare-and-subtract steps reach it.
+//   DIV 2: a 32-bit divide when both operands fit 32 bits, DIV 1 otherwise.
+template <int DIV>
+__device__ __forceinline__ uint64_t udiv_capped(uint64_t a, uint64_t b, uint64_t cap) {
+  if constexpr (DIV == 0) {
+    const uint64_t q = a / b;
+    return q < cap ? q : cap;
+  } else {
+    if constexpr (DIV == 2) {
+      if (((a | b) >> 32) == 0) {
+        const uint64_t q = (uint32_t)a / (uint32_t)b;
+        return q < cap ? q : cap;
+      }
+    }
+    const double e = __dmul_rn((double)a, __ddiv_rn(1.0, (double)b));
+    if (e >= (double)(cap + 2)) return cap;
+    uint64_t q = (uint64_t)e;
+    q = q ? q - 1 : 0;
+    uint64_t r = a - q * b;
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+      if (r >= b) {
+        r -= b;
+        q += 1;
+      }
+    return q < cap ? q : cap;
+  }
+}
+
+// Headroom of a node the pod FITS (node_fail_l returned 0): how many copies of the pod
+// AssumePod can add one after another before the node refuses the next, capped at `limit`,
+// and in `bind` the KSG_ROOM_* constraint that stops it (include/kschedgpu.h). The bounds in
+// the fail-code order: a GCE PD or a host port conflicts with the first copy (bound 1, and no
+// other bound of a fitting node is below 1, so no quotient is formed); cpu, memory and the
+// extended resources the pod requests bound it by floor((cap - used) / request), where the
+// fit check established 0 < request <= cap - used. Only called for a fitting lane: the lanes
+// of a tight cluster that do not fit pay for no division.
+template <bool COH, int DIV>
+__device__ __forceinline__ uint32_t node_room(const KsgDev& d, const PodCtx& c, uint32_t n, int64_t capc, int64_t capm,
+                                              int64_t usedc, int64_t usedm, uint32_t limit, int& bind) {
+  const uint32_t P = d.preds;
+  if ((P & KSG_PRED_NODISKCONFLICT) && c.n_pds) {
+    bind = KSG_ROOM_DISK;
+    return 1;
+  }
+  if ((P & KSG_PRED_PODFITSPORTS) && c.n_ports) {
+    bind = KSG_ROOM_PORTS;
+    return 1;
+  }
+  const uint64_t over = (uint64_t)limit + 1;  // "no bound at or below the limit"
+  uint64_t best = over;
+  bind = KSG_ROOM_LIMIT;
+  if ((P & KSG_PRED_PODFITSRESOURCES) && !c.zero_req) {
+    if (capc != 0 && c.req_cpu > 0) {
+      const uint64_t q = udiv_capped<DIV>((uint64_t)capc - (uint64_t)usedc, (uint64_t)c.req_cpu, over);
+      if (q < best) best = q, bind = KSG_ROOM_CPU;
+    }
+    if (capm != 0 && c.req_mem > 0) {
+      const uint64_t q = udiv_capped<DIV>((uint64_t)capm - (uint64_t)usedm, (uint64_t)c.req_mem, over);
+      if (q < best) best = q, bind = KSG_ROOM_MEMORY;
+    }
+  }
+  if ((d.ext_filters & KSG_EXT_SCALAR) && c.ext) {
+    for (uint32_t r = 0; r < d.n_scalar; ++r) {
+      const int64_t req = c.ext->scalar[r];
+      if (req > 0) {
+        const uint64_t cap = (uint64_t)d.scalar_cap[(size_t)r * d.n_nodes + n];
+        const uint64_t used = (uint64_t)ld_st<COH>(d.scalar_used + (size_t)r * d.n_nodes + n);
+        const uint64_t q = udiv_capped<DIV>(cap - used, (uint64_t)req, over);
+        if (q < best) best = q, bind = KSG_ROOM_SCALAR0 + (int)r;
+      }
+    }
+  }
+  // (a quotient of 0 only where used + request wrapped int64, which the header leaves
+  // unspecified: the node fits, so it still counts one copy)
+  return best > limit ? limit : best == 0 ? 1u : (uint32_t)best;
+}
+
 // BalancedResourceAllocation (kube-scheduler v1.10 balanced_resource_allocation.go,
 // not in this reference; parity unpinned) over the same requested totals as
 // LeastRequested, float64 op for op: fraction = requested / capacity (1 when

@@ -205,6 +205,14 @@ struct ksg_ctx {
   DevBuf<int64_t> d_pscores;
   DevBuf<uint8_t> d_ppart, d_pout;
   double last_prioritize_ms = 0.0;
+  // ksg_headroom_batch: the per-node counts of one chunk of pods (bounded: headroom_stage
+  // bytes, KSG_HEADROOM_STAGE_BYTES), and for the whole call uint64 total[n], uint32 max[n],
+  // uint32 fit[n], uint32 hist[n][KSG_HEADROOM_SLOTS], uint8 err[n] (one buffer, one copy out)
+  DevBuf<uint32_t> d_hcounts;
+  DevBuf<uint8_t> d_hout;
+  size_t headroom_stage = (size_t)64 << 20;
+  int headroom_div = 1;  // udiv_capped's variant (KSG_HEADROOM_DIV)
+  double last_headroom_ms = 0.0;
   std::vector<KsgPatch> patches;
 
   // host mirror

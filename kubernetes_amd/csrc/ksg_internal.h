@@ -262,6 +262,10 @@ typedef ksg_shard_record KsgRecordHdr;  // public layout (include/kschedgpu.h)
 #define KSG_EXPLAIN_TILE 256
 #define KSG_EXPLAIN_CHUNK 32
 
+// ksg_headroom_kernel (ksg_headroom.hip) keeps that tiling
+#define KSG_HEADROOM_TILE KSG_EXPLAIN_TILE
+#define KSG_HEADROOM_CHUNK KSG_EXPLAIN_CHUNK
+
 // ksg_prioritize_batch (ksg_prioritize.hip) keeps that tiling. Per (pod, node tile) the score
 // pass leaves one KsgPrioPart and the tile's best `top` entries (scores int64, nodes int32;
 // node -1 past the tile's fitting nodes); the merge pass reads them, one wave per pod.

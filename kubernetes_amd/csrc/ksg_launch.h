@@ -64,6 +64,11 @@ hipError_t ksg_launch_admit(const ksg_admission_set* sets, uint32_t n_sets, cons
 hipError_t ksg_launch_explain(const KsgDev& d, const ksg_pod* pods, const ksg_pod_ext* exts, const uint32_t* ids,
                               uint32_t n_pods, uint8_t* codes, uint32_t* hist, uint8_t* err, hipStream_t st);
 
+// ksg_headroom.hip (the per-pod arrays are indexed from `pods`; div: udiv_capped's variant)
+hipError_t ksg_launch_headroom(const KsgDev& d, const ksg_pod* pods, const ksg_pod_ext* exts, const uint32_t* ids,
+                               uint32_t n_pods, uint32_t limit, int div, uint32_t* counts, uint64_t* total,
+                               uint32_t* max_count, uint32_t* fit_count, uint32_t* hist, uint8_t* err, hipStream_t st);
+
 // ksg_prioritize.hip (all per-pod arrays are indexed from `pods`; dnorm = int32[n_pods][D + 1]:
 // a pod's ServiceAntiAffinity domain counts, then its TaintToleration max)
 bool ksg_prio_needs_reduce(const KsgDev& d, bool have_ext);

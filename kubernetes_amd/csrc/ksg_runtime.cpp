@@ -887,6 +887,10 @@ static int create_impl(const ksg_config* cfg, int device, int rank, int world, c
   c->srv_npt4_min = (uint32_t)env_int("KSG_SERVE_GRID_NPT4_MIN", c->srv_npt4_min, 0, INT32_MAX);
   c->srv_grid_ext = env_flag("KSG_SERVE_GRID_EXT", true);
   if (const char* rm = getenv("KSG_ROUND_MARGIN")) c->round_margin = std::min(std::max(atof(rm), 0.5), 4.0);
+  // ksg_headroom_batch: the staging budget of the per-node counts (a test knob: a chunk
+  // boundary at a small shape) and the quotient's variant (measurements)
+  c->headroom_stage = (size_t)env_int("KSG_HEADROOM_STAGE_BYTES", (int64_t)c->headroom_stage, 4, (int64_t)1 << 40);
+  c->headroom_div = (int)env_int("KSG_HEADROOM_DIV", c->headroom_div, 0, 2);
   // The exchange path (shard scan, all-gather of per-shard records, replicated
   // resolve) runs for world > 1, and for a 1-rank RCCL communicator when the caller
   // passes an nccl_id with world == 1 (RCCL itself exercised on a single GPU).
@@ -2106,6 +2110,92 @@ int ksg_last_prioritize_ms(ksg_ctx* c, double* ms) {
   if (!c || !ms) return KSG_ERR_ARG;
   KSG_LOCK(c);
   *ms = c->last_prioritize_ms;
+  return KSG_OK;
+}
+
+// How many copies of each pod every node can take: one grid-wide pass (ksg_headroom.hip) over
+// the device state as it stands. Protocol and validation are ksg_explain_batch's; no uid is
+// looked at and note_requests is NOT called (no score is computed), so later batches take the
+// path they would have taken. A sharded context covers the whole (replicated) cluster alone.
+int ksg_headroom_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
+                       uint32_t n_ids, uint32_t limit, uint64_t* total, uint32_t* fit_count, uint32_t* max_count,
+                       uint32_t* bind_hist, uint32_t* counts, uint8_t* err) {
+  if (!c || (n && (!pods || !total || !fit_count || !max_count || !bind_hist || !err))) return KSG_ERR_ARG;
+  KSG_LOCK(c);
+  if (limit == 0) return fail(c, KSG_ERR_ARG, "limit 0");
+  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
+  if (ext && !c->ext_on) return fail(c, KSG_ERR_STATE, "extensions are off");
+  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
+  if (int rc0 = flush_deferred(c)) return rc0;
+  if (int rs = cluster_ok(c)) return rs;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->last_headroom_ms = 0.0;
+  if (n == 0) return KSG_OK;
+  if (c->N == 0) return KSG_NONODES;
+  if (n_ids && !ids) return fail(c, KSG_ERR_ARG, "ids missing");
+  int rc;
+  for (uint32_t i = 0; i < n; ++i) {
+    if ((rc = check_pod(c, pods + i, ids, n_ids))) return rc;
+    if (ext && ((rc = check_ext_range(c, ext + i, n_ids)) || (rc = check_taint_ids(c, ext + i, ids)))) return rc;
+  }
+  if ((rc = flush_patches(c))) return rc;
+  if ((rc = upload_pods(c, pods, n, ids, n_ids))) return rc;
+  const ksg_pod_ext* dext = nullptr;
+  if (ext) {  // (no record: node_fail and node_room skip the extension filters, as an all-zero record passes them)
+    if ((rc = c->d_pext.grow(c, n))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_pext, ext, (size_t)n * sizeof(ksg_pod_ext), hipMemcpyHostToDevice, c->st));
+    dext = c->d_pext;
+  }
+  // the per-pod results of the whole call: uint64 total[n], uint32 max[n], uint32 fit[n],
+  // uint32 hist[n][KSG_HEADROOM_SLOTS], uint8 err[n]; the per-node counts in a bounded staging
+  // buffer, a chunk of pods at a time (whole pod chunks of the kernel, at least one pod)
+  const size_t o_max = (size_t)n * 8, o_fit = o_max + (size_t)n * 4, o_hist = o_fit + (size_t)n * 4;
+  const size_t hb = (size_t)n * KSG_HEADROOM_SLOTS * sizeof(uint32_t), o_err = o_hist + hb, ob = o_err + n;
+  if ((rc = c->d_hout.grow(c, ob)) || (rc = c->h_dn.grow(c, ob))) return rc;
+  uint8_t* const ho = c->d_hout;
+  HIPCHK(c, hipMemsetAsync(ho, 0, ob, c->st));
+  uint32_t per = 1u << 20;  // pods per launch (the grid's y extent stays far below 65,535)
+  if (counts) {
+    per = (uint32_t)std::min<size_t>(per, std::max<size_t>(c->headroom_stage / ((size_t)c->N * sizeof(uint32_t)), 1));
+    if (per > KSG_HEADROOM_CHUNK) per -= per % KSG_HEADROOM_CHUNK;
+    per = std::min(per, n);
+    if ((rc = c->d_hcounts.grow(c, (size_t)per * c->N))) return rc;
+  }
+  if (!c->ev_x0) {
+    HIPCHK(c, hipEventCreate(&c->ev_x0));
+    HIPCHK(c, hipEventCreate(&c->ev_x1));
+  }
+  for (uint32_t a = 0; a < n; a += per) {
+    const uint32_t m = std::min(per, n - a);
+    HIPCHK(c, hipEventRecord(c->ev_x0, c->st));
+    HIPCHK(c, ksg_launch_headroom(c->dev, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m, limit, c->headroom_div,
+                                  counts ? c->d_hcounts.p : nullptr, reinterpret_cast<uint64_t*>(ho) + a,
+                                  reinterpret_cast<uint32_t*>(ho + o_max) + a, reinterpret_cast<uint32_t*>(ho + o_fit) + a,
+                                  reinterpret_cast<uint32_t*>(ho + o_hist) + (size_t)a * KSG_HEADROOM_SLOTS,
+                                  ho + o_err + a, c->st));
+    HIPCHK(c, hipEventRecord(c->ev_x1, c->st));
+    if (counts)
+      HIPCHK(c, hipMemcpyAsync(counts + (size_t)a * c->N, c->d_hcounts, (size_t)m * c->N * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost, c->st));
+    if (a + per >= n)  // the last chunk's wait also brings the per-pod results back
+      HIPCHK(c, hipMemcpyAsync(c->h_dn, ho, ob, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));  // (the staging buffer is reused by the next chunk)
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_x0, c->ev_x1));
+    c->last_headroom_ms += ms;
+  }
+  memcpy(total, c->h_dn, (size_t)n * 8);
+  memcpy(max_count, c->h_dn + o_max, (size_t)n * 4);
+  memcpy(fit_count, c->h_dn + o_fit, (size_t)n * 4);
+  memcpy(bind_hist, c->h_dn + o_hist, hb);
+  memcpy(err, c->h_dn + o_err, n);
+  return KSG_OK;
+}
+
+int ksg_last_headroom_ms(ksg_ctx* c, double* ms) {
+  if (!c || !ms) return KSG_ERR_ARG;
+  KSG_LOCK(c);
+  *ms = c->last_headroom_ms;
   return KSG_OK;
 }
 

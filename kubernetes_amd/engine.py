@@ -334,6 +334,38 @@ class DeviceScheduler:
         self._lib.ksg_last_prioritize_ms(self._ctx, C.byref(ms))
         return ms.value
 
+    def headroom(self, batch: PodBatch, limit: int, want_counts: bool = True):
+        """ksg_headroom_batch: how many copies of every pod of `batch` each node of the cluster
+        as it stands can take (placed one after another on that node, capped at `limit`), in one
+        device pass, committing nothing.
+        -> (total uint64[n], fit_count uint32[n], max_count uint32[n], bind_hist uint32[n,
+        HEADROOM_SLOTS], counts uint32[n, N] | None, err uint8[n]): per pod the sum of the counts,
+        the nodes with a non-zero count, the largest count, the nodes per binding constraint
+        (abi.ROOM_*), the per-node counts (want_counts), and abi.HEADROOM_ERR_* for a pod whose
+        ServiceAffinity peer is on an unknown host or that has a negative request (rows zero)."""
+        n = len(batch)
+        pods = np.ascontiguousarray(batch.pods, dtype=abi.POD_DTYPE)
+        ids = _u32(batch.ids if len(batch.ids) else np.zeros(1, np.uint32))
+        ext = None if batch.ext is None else np.ascontiguousarray(batch.ext, dtype=abi.POD_EXT_DTYPE)
+        total = np.zeros(n, np.uint64)
+        fit = np.zeros(n, np.uint32)
+        mx = np.zeros(n, np.uint32)
+        hist = np.zeros((n, abi.HEADROOM_SLOTS), np.uint32)
+        counts = np.zeros((n, self.n_nodes), np.uint32) if want_counts else None
+        err = np.zeros(n, np.uint8)
+        rc = self._lib.ksg_headroom_batch(self._ctx, abi.ptr(pods), abi.ptr(ext), n, abi.ptr(ids), len(batch.ids),
+                                          int(limit), abi.ptr(total), abi.ptr(fit), abi.ptr(mx), abi.ptr(hist),
+                                          abi.ptr(counts) if want_counts and counts.size else None, abi.ptr(err))
+        if rc not in (abi.KSG_OK, abi.KSG_NONODES):
+            self._err(rc)
+        return total, fit, mx, hist, counts, err
+
+    def last_headroom_ms(self) -> float:
+        """Device ms of the last headroom()'s kernel launches (HIP events)."""
+        ms = C.c_double(0)
+        self._lib.ksg_last_headroom_ms(self._ctx, C.byref(ms))
+        return ms.value
+
     def set_window(self, window: int):
         """Pods per speculative window (0 = exact one-pod-at-a-time kernel)."""
         rc = self._lib.ksg_set_window(self._ctx, int(window))

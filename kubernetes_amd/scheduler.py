@@ -333,6 +333,47 @@ class GPUScheduler:
                 out.append([(names[int(n)], int(s)) for n, s in zip(tn[i], ts[i]) if n >= 0])
         return out
 
+    # ---- dry run: how many copies of a pod fit ----------------------------------------
+    ROOM_NAMES = {abi.ROOM_LIMIT: "limit", abi.ROOM_DISK: "disk", abi.ROOM_PORTS: "ports", abi.ROOM_CPU: "cpu",
+                  abi.ROOM_MEMORY: "memory", **{abi.ROOM_SCALAR0 + r: f"scalar{r}" for r in range(abi.MAX_SCALAR)}}
+
+    def headroom(self, pods: Sequence[Pod], minion_lister, limit: int = 1 << 16, per_node: bool = False) -> list:
+        """How many copies of each pod (a template) fit now: per pod a record from one
+        ksg_headroom_batch, {"total": the copies the nodes take together (each node filled on its
+        own, at most `limit` per node), "nodes": the nodes that take at least one, "largest": the
+        most one node takes, "binding": {constraint name: nodes it stops}, names "limit", "disk",
+        "ports", "cpu", "memory", "scalar<r>"}, and with per_node=True "per_node": {host name:
+        count} for the nodes that take at least one. total >= r says a gang of r fits, except
+        under a ServiceAffinity predicate while the pod's service has no peer, where it is an
+        upper bound. Nothing is committed or drawn, and no pod is assumed. A SchedulingError
+        instead of a record: the pod's ServiceAffinity peer is on an unknown host; a ValueError:
+        the pod has a negative request; NoMinionsError entries without nodes."""
+        nodes = minion_lister.list()
+        if len(nodes) == 0:
+            return [NoMinionsError() for _ in pods]
+        self._sync(nodes)
+        if not pods:
+            return []
+        b = PodBatchBuilder(self.view, self.aff_labels)
+        for p in pods:
+            b.add(p, 0)  # (the call ignores uids)
+        total, fit, mx, hist, counts, err = self.engine.headroom(b.build(), limit, want_counts=per_node)
+        names = self.view.names
+        out: list = []
+        for i in range(len(pods)):
+            if err[i] == abi.HEADROOM_ERR_PEER:
+                out.append(SchedulingError("service affinity peer is not on a known node"))
+                continue
+            if err[i]:
+                out.append(ValueError("negative resource request"))
+                continue
+            rec = {"total": int(total[i]), "nodes": int(fit[i]), "largest": int(mx[i]),
+                   "binding": {self.ROOM_NAMES[s]: int(hist[i, s]) for s in range(1, hist.shape[1]) if hist[i, s]}}
+            if per_node:
+                rec["per_node"] = {names[int(n)]: int(counts[i, n]) for n in counts[i].nonzero()[0]}
+            out.append(rec)
+        return out
+
 
 def new_gpu_scheduler(config: SchedulerConfig, pod_lister, service_lister=None, random=None,
                       device: int = 0) -> GPUScheduler:
