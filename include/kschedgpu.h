@@ -545,7 +545,7 @@ int ksg_read_ext_used(ksg_ctx* ctx, int64_t* used);
  * state with the whole batch committed, the state a retry of the pod would meet. It
  * equals what the sequential reference reported for pod i whenever no pod after i in
  * the batch was placed; otherwise it may differ on the nodes that later pods took
- * (the state "as of pod i" is not reconstructed).
+ * (this call does not go back to the state "as of pod i": ksg_explain_without, below, does).
  * Every node of the cluster is covered on every rank of a sharded context (node state
  * is replicated), with no exchange: ranks need not make the call together.
  * uid is ignored: a pod whose uid is committed, or the same pod twice, is legal.
@@ -566,6 +566,52 @@ int ksg_explain_batch(ksg_ctx* ctx, const ksg_pod* pods, const ksg_pod_ext* ext 
 /* Device time (ms) of the last ksg_explain_batch's kernel launches, from HIP events
  * on the context's stream (the copies out are not in it). Diagnostics. */
 int ksg_last_explain_ms(ksg_ctx* ctx, double* ms);
+
+/* ---- FitError reports with committed pods taken away ----
+ * ksg_explain_batch against an earlier or a hypothetical state: absent_uids is an ordered
+ * list of n_absent committed pods and first_absent[i] pod i's position in it. Row i of
+ * codes, hist and err is bit for bit what ksg_explain_batch would write for pod i if
+ * ksg_remove_pod had first been called for every uid of
+ * absent_uids[first_absent[i] .. n_absent). The order of those removals does not matter:
+ * the requested cpu, memory and extended-resource totals subtract with the reference's
+ * wrapping arithmetic, as ksg_remove_pod does; a host-port / GCE-PD conflict bit stays
+ * while any holder remains on the node; the ServiceAffinity peer is the first remaining
+ * member of the pod's service in commit order. A listed pod on a host outside the node
+ * list changes only the peer. A peer that becomes an unknown host gives err[i] = 1 and
+ * zero rows, as ksg_explain_batch reports it; a peer that stops being one clears the error.
+ * Two uses:
+ *   - the state AS OF POD i of the last batch, which is what the sequential reference
+ *     reported for it (generic_scheduler.go:30-44, 100-128): the list is the batch's
+ *     placed pods in order, first_absent[i] the number placed before pod i;
+ *   - preemption feasibility, "on which nodes would this pod fit if every lower-priority
+ *     pod were evicted": the list is the removable pods sorted by descending priority,
+ *     first_absent[i] the first entry below pod i's priority. The library knows no
+ *     priorities; the caller's ordering carries them.
+ * n_absent == 0, or every first_absent[i] == n_absent: the output is ksg_explain_batch's.
+ * Nothing is removed. The call changes nothing a later call can observe: not the
+ * committed totals, the generator state, the uid bookkeeping, the extended-resource usage
+ * or the results of any later batch, and like ksg_explain_batch it does not look at the
+ * pods' requests to decide between the int32 and the int64 score kernels (it computes no
+ * score), so it leaves the path later batches take as it was.
+ * Protocol and validation are ksg_explain_batch's: ext, uid, n == 0 (KSG_OK, nothing
+ * written), hist or err NULL, KSG_ERR_STATE while a ksg_schedule_begin is pending or for
+ * ext without extensions, KSG_NONODES for an empty node list, every node covered on every
+ * rank of a sharded context with no exchange. The last batch's commits are in the list's
+ * reach as soon as ksg_schedule_batch has returned. Also KSG_ERR_ARG, with nothing
+ * written: an absent_uids entry that is not a committed uid, the same uid twice,
+ * first_absent[i] > n_absent, absent_uids or first_absent NULL with n_absent > 0.
+ * The pods are processed in chunks whose per-node codes fit a device staging budget
+ * (64 MiB; the environment variable KSG_EXPLAIN_WITHOUT_STAGE_BYTES, read by ksg_create,
+ * overrides it). */
+int ksg_explain_without(ksg_ctx* ctx, const ksg_pod* pods, const ksg_pod_ext* ext /* NULL: all-zero */,
+                        uint32_t n, const uint32_t* ids, uint32_t n_ids,
+                        const uint64_t* absent_uids /* n_absent; may be NULL iff n_absent == 0 */,
+                        uint32_t n_absent, const uint32_t* first_absent /* n; may be NULL iff n_absent == 0 */,
+                        uint8_t* codes /* optional, n * n_nodes */, uint32_t* hist /* n * KSG_EXPLAIN_SLOTS */,
+                        uint8_t* err /* n */);
+/* Device time (ms) of the last ksg_explain_without's kernel launches, from HIP events on
+ * the context's stream (the table upload and the copies out are not in it). Diagnostics. */
+int ksg_last_explain_without_ms(ksg_ctx* ctx, double* ms);
 
 /* ---- Ranked hosts for many pods (prioritizeNodes + the sorted HostPriorityList) ----
  * One device pass filters and scores n pods against every node, as ksg_evaluate does

@@ -236,6 +236,8 @@ EXPORTS = [
     "ksg_last_prioritize_ms",
     "ksg_headroom_batch",
     "ksg_last_headroom_ms",
+    "ksg_explain_without",
+    "ksg_last_explain_without_ms",
 ]
 
 # int (*ksg_allgather_fn)(void* user, const void* send, void* recv, uint64_t bytes)
@@ -316,6 +318,9 @@ def load_library() -> C.CDLL:
         # (ctx, pods, ext | NULL, n, ids, n_ids, limit, total, fit_count, max_count, bind_hist, counts | NULL, err)
         "ksg_headroom_batch": (C.c_int, [vp, vp, vp, U32, vp, U32, U32, vp, vp, vp, vp, vp, vp]),
         "ksg_last_headroom_ms": (C.c_int, [vp, P(C.c_double)]),
+        # (ctx, pods, ext | NULL, n, ids, n_ids, absent_uids | NULL, n_absent, first_absent | NULL, codes | NULL, hist, err)
+        "ksg_explain_without": (C.c_int, [vp, vp, vp, U32, vp, U32, vp, U32, vp, vp, vp, vp]),
+        "ksg_last_explain_without_ms": (C.c_int, [vp, P(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

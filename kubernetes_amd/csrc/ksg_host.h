@@ -213,6 +213,13 @@ struct ksg_ctx {
   size_t headroom_stage = (size_t)64 << 20;
   int headroom_div = 1;  // udiv_capped's variant (KSG_HEADROOM_DIV)
   double last_headroom_ms = 0.0;
+  // ksg_explain_without (ksg_without.cpp): the per-node codes of one chunk of pods (bounded:
+  // without_stage bytes, KSG_EXPLAIN_WITHOUT_STAGE_BYTES), the histograms then the error flags of
+  // the whole call, and the call's tables (KsgWithout's arrays, one buffer, one copy in)
+  DevBuf<uint8_t> d_wcodes, d_whist, d_wtab;
+  HostBuf h_wtab;
+  size_t without_stage = (size_t)64 << 20;
+  double last_without_ms = 0.0;
   std::vector<KsgPatch> patches;
 
   // host mirror

@@ -262,6 +262,24 @@ typedef ksg_shard_record KsgRecordHdr;  // public layout (include/kschedgpu.h)
 #define KSG_EXPLAIN_TILE 256
 #define KSG_EXPLAIN_CHUNK 32
 
+// ksg_explain_without_kernel (ksg_explain_without.hip) keeps that tiling. Its read-only tables
+// (built per call by ksg_without.cpp) describe an ordered list of n_absent committed pods; pod p
+// is explained without the pods at list indices >= first_absent[p].
+struct KsgWithout {
+  const uint64_t* touched;       // [nw] nodes that carry a listed pod
+  const uint32_t* nd_off;        // [N + 1] CSR by node rank of the listed pods on the node ...
+  const uint32_t* nd_idx;        // [nd_n] ... their list indices, ascending within a row
+  const uint64_t* nd_sum;        // [2 + n_scalar][nd_n] wrapping sums of cpu, memory and the extended
+                                 // resources over the entries from this one to the end of its row
+  const uint32_t* cf_off;        // [N + 1] CSR by node rank of the conflict keys only listed pods hold ...
+  const uint32_t* cf_key;        // ... the keys, ascending within a row
+  const uint32_t* cf_min;        // ... the smallest list index among a key's holders on the node
+  const uint32_t* first_absent;  // [n_pods] a pod's position in the list (n_absent: nothing is taken away)
+  const int32_t* peer;           // [n_pods] its ServiceAffinity peer as of that position (svc_peer's codes);
+                                 // nullptr without a ServiceAffinity predicate
+  uint32_t nd_n, n_absent;
+};
+
 // ksg_headroom_kernel (ksg_headroom.hip) keeps that tiling
 #define KSG_HEADROOM_TILE KSG_EXPLAIN_TILE
 #define KSG_HEADROOM_CHUNK KSG_EXPLAIN_CHUNK

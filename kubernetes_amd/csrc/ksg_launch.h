@@ -64,6 +64,11 @@ hipError_t ksg_launch_admit(const ksg_admission_set* sets, uint32_t n_sets, cons
 hipError_t ksg_launch_explain(const KsgDev& d, const ksg_pod* pods, const ksg_pod_ext* exts, const uint32_t* ids,
                               uint32_t n_pods, uint8_t* codes, uint32_t* hist, uint8_t* err, hipStream_t st);
 
+// ksg_explain_without.hip (w.first_absent and w.peer are indexed from `pods`, like the outputs)
+hipError_t ksg_launch_explain_without(const KsgDev& d, const KsgWithout& w, const ksg_pod* pods, const ksg_pod_ext* exts,
+                                      const uint32_t* ids, uint32_t n_pods, uint8_t* codes, uint32_t* hist, uint8_t* err,
+                                      hipStream_t st);
+
 // ksg_headroom.hip (the per-pod arrays are indexed from `pods`; div: udiv_capped's variant)
 hipError_t ksg_launch_headroom(const KsgDev& d, const ksg_pod* pods, const ksg_pod_ext* exts, const uint32_t* ids,
                                uint32_t n_pods, uint32_t limit, int div, uint32_t* counts, uint64_t* total,

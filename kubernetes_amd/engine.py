@@ -300,6 +300,40 @@ class DeviceScheduler:
         self._lib.ksg_last_explain_ms(self._ctx, C.byref(ms))
         return ms.value
 
+    def explain_without(self, batch: PodBatch, absent_uids, first_absent, want_codes: bool = True):
+        """ksg_explain_without: explain() against the state with committed pods taken away.
+        `absent_uids` is an ordered list of committed uids and `first_absent[i]` pod i's position
+        in it: pod i is explained as if every pod of absent_uids[first_absent[i]:] had been
+        removed first (nothing is). The batch's placed uids in order with the number placed before
+        pod i give the state as of pod i; removable pods sorted by descending priority with the
+        first entry below pod i's priority give preemption feasibility.
+        -> (codes | None, hist, err) as explain()."""
+        n = len(batch)
+        pods = np.ascontiguousarray(batch.pods, dtype=abi.POD_DTYPE)
+        ids = _u32(batch.ids if len(batch.ids) else np.zeros(1, np.uint32))
+        ext = None if batch.ext is None else np.ascontiguousarray(batch.ext, dtype=abi.POD_EXT_DTYPE)
+        uids = np.ascontiguousarray(absent_uids, dtype=np.uint64)
+        fa = _u32(first_absent)
+        if len(fa) != n:
+            raise ValueError(f"first_absent has {len(fa)} entries for {n} pods")
+        codes = np.zeros((n, self.n_nodes), np.uint8) if want_codes else None
+        hist = np.zeros((n, abi.EXPLAIN_SLOTS), np.uint32)
+        err = np.zeros(n, np.uint8)
+        rc = self._lib.ksg_explain_without(self._ctx, abi.ptr(pods), abi.ptr(ext), n, abi.ptr(ids), len(batch.ids),
+                                           abi.ptr(uids) if len(uids) else None, len(uids),
+                                           abi.ptr(fa) if n else None,
+                                           abi.ptr(codes) if want_codes and codes.size else None, abi.ptr(hist),
+                                           abi.ptr(err))
+        if rc not in (abi.KSG_OK, abi.KSG_NONODES):
+            self._err(rc)
+        return codes, hist, err
+
+    def last_explain_without_ms(self) -> float:
+        """Device ms of the last explain_without()'s kernel launches (HIP events)."""
+        ms = C.c_double(0)
+        self._lib.ksg_last_explain_without_ms(self._ctx, C.byref(ms))
+        return ms.value
+
     def prioritize(self, batch: PodBatch, top: int = 0, want_scores: bool = False):
         """ksg_prioritize_batch: filter and score every pod of `batch` against every node of the
         cluster as it stands, in one device pass, committing nothing.

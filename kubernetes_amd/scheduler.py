@@ -252,14 +252,19 @@ class GPUScheduler:
         return host
 
     # ---- batch path (persistent kernel) -------------------------------------
-    def schedule_batch(self, pods: Sequence[Pod], minion_lister, rng_state: int, explain: bool = False):
+    def schedule_batch(self, pods: Sequence[Pod], minion_lister, rng_state: int, explain=False):
         """Schedule pods in order without host round-trips; each success is assumed
         (committed) before the next pod. -> (hosts or None per pod, rng_state).
         explain=True: -> (hosts, rng_state, errors), errors[i] None for a placed pod, else the
         error Schedule would return for it: a FitError (with `counts`) built from one
         ksg_explain_batch over the batch's unschedulable pods, or a SchedulingError for a
         ServiceAffinity peer on an unknown host (NoMinionsError without nodes). The report is
-        against the state after the whole batch: the state a retry of the pod would meet."""
+        against the state after the whole batch: the state a retry of the pod would meet.
+        explain="as_of": the same triple, each error against the state as of its pod, with the
+        batch's later placements taken away again: the FitError pod-by-pod schedule() calls
+        would have raised, from one ksg_explain_without over the batch's unschedulable pods."""
+        if explain not in (False, True, "as_of"):
+            raise ValueError(f"explain={explain!r}: False, True or 'as_of'")
         nodes = minion_lister.list()
         if len(nodes) == 0:
             if explain:
@@ -284,16 +289,27 @@ class GPUScheduler:
             else:
                 hosts.append(None)
         if explain:
-            return hosts, rng_state, self._explain(pods, batch, [i for i, h in enumerate(hosts) if h is None])
+            placed = None
+            if explain == "as_of":  # the placed uids in order; a pod's position: the number placed before it
+                placed = [uids[i] for i in range(len(pods)) if out[i] >= 0]
+            return hosts, rng_state, self._explain(pods, batch, [i for i, h in enumerate(hosts) if h is None], out, placed)
         return hosts, rng_state
 
-    def _explain(self, pods: Sequence[Pod], batch: PodBatch, idx: List[int]) -> list:
-        """errors[i] for the pods `idx` of a batch that found no node: one device pass."""
+    def _explain(self, pods: Sequence[Pod], batch: PodBatch, idx: List[int], out=None, placed=None) -> list:
+        """errors[i] for the pods `idx` of a batch that found no node: one device pass
+        (`placed`: against the state as of each pod, the later of these uids taken away)."""
         errors: list = [None] * len(pods)
         if not idx:
             return errors
         sub = PodBatch(batch.pods[idx], batch.ids, None if batch.ext is None else batch.ext[idx])
-        codes, hist, err = self.engine.explain(sub)
+        if placed is None:
+            codes, hist, err = self.engine.explain(sub)
+        else:
+            before, k = [], 0  # placed before pod i
+            for o in out:
+                before.append(k)
+                k += o >= 0
+            codes, hist, err = self.engine.explain_without(sub, placed, [before[i] for i in idx])
         names = self.view.names
         for j, i in enumerate(idx):
             if err[j]:
