@@ -418,6 +418,31 @@ int ksg_shard(ksg_ctx* ctx, uint32_t* lo, uint32_t* hi);
  * the node) back to the host, for state checks. */
 int ksg_read_requested(ksg_ctx* ctx, int64_t* milli_cpu, int64_t* memory);
 
+/* Copy the rest of the committed per-node pod state back to the host, for state
+ * checks (diagnostics, like ksg_read_requested; with it and ksg_read_ext_used this
+ * is every word a commit, ksg_add_pod, ksg_remove_pod or ksg_batch_unwind changes).
+ * The state is a function of the ordered list of live pods and their hosts:
+ *   keymap[k * nw + n / 64] bit n % 64   some live pod on node n lists conflict key k
+ *                                        among its host ports or GCE PDs
+ *   svc_cnt[s * n_nodes + n]             live pods on node n whose service list holds s
+ *   svc_bits[s * nw + n / 64] bit n % 64 svc_cnt[s][n] > 0
+ *   svc_total[s]                         live pods of service s, on any host
+ *   svc_max[s]                           the largest count of service s on one host, hosts
+ *                                        outside the node list included (spreading.go:72-80)
+ *   svc_peer[s]                          -1: no live pod of s; else the host of the one
+ *                                        added earliest (predicates.go:293), -2 if that
+ *                                        host is not a node
+ * with nw = ceil(n_nodes / 64), k < max_conflict_keys, s < n_services. Bits at or above
+ * n_nodes in a last word are zero. Every field is specified; none is left to the
+ * implementation. Any pointer may be NULL. The call reads what the device holds: pending
+ * patches of ksg_add_pod / ksg_remove_pod are applied first, as any kernel would see them,
+ * but the host's replay of the last batch is not consulted. KSG_ERR_ARG before the first
+ * ksg_set_cluster. On a sharded context, as with ksg_read_requested, the node state is
+ * replicated and every rank returns all of it. */
+int ksg_read_state(ksg_ctx* ctx, uint64_t* keymap /* max_conflict_keys x ceil(n_nodes/64) */,
+                   int32_t* svc_cnt /* n_services x n_nodes */, uint64_t* svc_bits /* n_services x ceil(n_nodes/64) */,
+                   int32_t* svc_max, int32_t* svc_total, int32_t* svc_peer /* n_services each */);
+
 /* ---- kubelet admission -------------------------------
  * The node agent re-checks its own pods with the scheduler's predicates
  * (handleNotFittingPods, pkg/kubelet/kubelet.go:1716-1771):

@@ -216,6 +216,7 @@ EXPORTS = [
     "ksg_batch_unwind",
     "ksg_shard",
     "ksg_read_requested",
+    "ksg_read_state",
     "ksg_shard_range",
     "ksg_merge_records",
     "ksg_set_allgather",
@@ -294,6 +295,8 @@ def load_library() -> C.CDLL:
         "ksg_batch_unwind": (C.c_int, [vp, vp, vp, U32, U32, vp, P(U32)]),
         "ksg_shard": (C.c_int, [vp, P(U32), P(U32)]),
         "ksg_read_requested": (C.c_int, [vp, vp, vp]),
+        # (ctx, keymap, svc_cnt, svc_bits, svc_max, svc_total, svc_peer; each may be NULL)
+        "ksg_read_state": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
         "ksg_shard_range": (C.c_int, [U32, C.c_int, C.c_int, P(U32), P(U32)]),
         "ksg_merge_records": (C.c_int, [vp, U32, U32, U32, C.c_int, P(U64), U64, P(I32), P(I64), P(U64)]),
         "ksg_set_allgather": (C.c_int, [vp, ALLGATHER_FN, vp]),

@@ -1725,6 +1725,30 @@ int ksg_read_requested(ksg_ctx* c, int64_t* milli_cpu, int64_t* memory) {
   return KSG_OK;
 }
 
+// The rest of the mutable per-node state, as the device holds it: like ksg_read_requested,
+// and on purpose without flush_deferred (the host mirror's opinion is not what is read).
+int ksg_read_state(ksg_ctx* c, uint64_t* keymap, int32_t* svc_cnt, uint64_t* svc_bits, int32_t* svc_max,
+                   int32_t* svc_total, int32_t* svc_peer) {
+  if (!c || !c->have_cluster) return KSG_ERR_ARG;
+  KSG_LOCK(c);
+  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = flush_patches(c);
+  if (rc) return rc;
+  const size_t K = c->cfg.max_conflict_keys, S = c->S, N = c->N, nw = c->nw;
+  auto out = [&](void* dst, const void* src, size_t bytes) {
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->st) : hipSuccess;
+  };
+  HIPCHK(c, out(keymap, c->dev.keymap, K * nw * 8));
+  HIPCHK(c, out(svc_cnt, c->dev.svc_cnt, S * N * 4));
+  HIPCHK(c, out(svc_bits, c->dev.svc_bits, S * nw * 8));
+  HIPCHK(c, out(svc_max, c->dev.svc_max, S * 4));
+  HIPCHK(c, out(svc_total, c->dev.svc_total, S * 4));
+  HIPCHK(c, out(svc_peer, c->dev.svc_peer, S * 4));
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  return KSG_OK;
+}
+
 // ---- kubelet admission (ksg_admit.hip) ------------------------------------
 static int admit_impl(ksg_ctx* c, int mode, const ksg_admission_set* sets, uint32_t n_sets, const ksg_pod* pods,
                       uint32_t n_pods, const uint32_t* ids, uint32_t n_ids, const uint32_t* pairs, uint32_t n_pairs,

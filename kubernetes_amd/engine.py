@@ -85,6 +85,7 @@ class DeviceScheduler:
             raise KsgError(rc, "ksg_create failed (see stderr)")
         self.cfg = cfg
         self.n_nodes = 0
+        self.n_services = 0
         self.n_scalar = 0
         self.world = world
         self.rank = rank
@@ -146,6 +147,7 @@ class DeviceScheduler:
         if rc != abi.KSG_OK:
             self._err(rc)
         self.n_nodes = len(nodes)
+        self.n_services = int(cl.n_services)
 
     # ---- extensions (include/kschedgpu.h; parity unpinned) ---------------------
     def set_extensions(self, ext: abi.KsgExtConfig):
@@ -522,6 +524,25 @@ class DeviceScheduler:
         if rc != abi.KSG_OK:
             self._err(rc)
         return c[: self.n_nodes], m[: self.n_nodes]
+
+    def read_state(self) -> dict:
+        """The rest of the committed per-node pod state as the device holds it (ksg_read_state):
+        keymap uint64[max_conflict_keys, nw], svc_cnt int32[S, N], svc_bits uint64[S, nw],
+        svc_max / svc_total / svc_peer int32[S], with nw = ceil(N / 64)."""
+        return _read_state(lambda *a: self._lib.ksg_read_state(self._ctx, *a), self._err,
+                           int(self.cfg.max_conflict_keys), self.n_services, self.n_nodes)
+
+
+def _read_state(call, err, n_keys: int, n_services: int, n_nodes: int) -> dict:
+    nw = (n_nodes + 63) // 64
+    shapes = (("keymap", np.uint64, (n_keys, nw)), ("svc_cnt", np.int32, (n_services, n_nodes)),
+              ("svc_bits", np.uint64, (n_services, nw)), ("svc_max", np.int32, (n_services,)),
+              ("svc_total", np.int32, (n_services,)), ("svc_peer", np.int32, (n_services,)))
+    bufs = [np.zeros(max(int(np.prod(s)), 1), t) for _, t, s in shapes]
+    rc = call(*[abi.ptr(b) for b in bufs])
+    if rc != abi.KSG_OK:
+        err(rc)
+    return {name: b[: int(np.prod(s))].reshape(s) for (name, _, s), b in zip(shapes, bufs)}
 
 
 def gloo_allgather(group=None):

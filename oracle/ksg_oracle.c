@@ -1135,6 +1135,33 @@ void orc_read_requested(orc *o, int64_t *c, int64_t *m) {
   if (m) memcpy(m, o->used_m, (size_t)o->N * 8);
 }
 
+/* the rest of the pod state in ksg_read_state's layout: a bitmap bit is key_ref > 0 or
+ * svc_cnt > 0, the peer is first_peer's host (-1 none, -2 not a node) */
+void orc_read_state(orc *o, uint64_t *keymap, int32_t *svc_cnt, uint64_t *svc_bits, int32_t *svc_max,
+                    int32_t *svc_total, int32_t *svc_peer) {
+  const size_t N = o->N, nw = (N + 63) / 64;
+  if (keymap) {
+    memset(keymap, 0, (size_t)o->cfg.max_conflict_keys * nw * 8);
+    for (size_t k = 0; k < o->cfg.max_conflict_keys; ++k)
+      for (size_t n = 0; n < N; ++n)
+        if (o->key_ref[k * N + n] > 0) keymap[k * nw + n / 64] |= 1ULL << (n % 64);
+  }
+  if (svc_cnt) memcpy(svc_cnt, o->svc_cnt, (size_t)o->S * N * 4);
+  if (svc_bits) {
+    memset(svc_bits, 0, (size_t)o->S * nw * 8);
+    for (size_t s = 0; s < o->S; ++s)
+      for (size_t n = 0; n < N; ++n)
+        if (o->svc_cnt[s * N + n] > 0) svc_bits[s * nw + n / 64] |= 1ULL << (n % 64);
+  }
+  if (svc_max) memcpy(svc_max, o->svc_max, (size_t)o->S * 4);
+  if (svc_total) memcpy(svc_total, o->svc_total, (size_t)o->S * 4);
+  if (svc_peer)
+    for (uint32_t s = 0; s < o->S; ++s) {
+      const opod *p = first_peer(o, s);
+      svc_peer[s] = !p ? -1 : p->host < o->N ? (int32_t)p->host : -2;
+    }
+}
+
 /* the extended-resource usage [n_scalar][N] (ksg_read_ext_used) */
 void orc_read_ext_used(orc *o, int64_t *used) {
   if (used && o->sused) memcpy(used, o->sused, (size_t)o->ext.n_scalar * o->N * 8);

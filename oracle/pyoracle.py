@@ -13,7 +13,7 @@ import subprocess
 import numpy as np
 
 from kubernetes_amd import abi
-from kubernetes_amd.engine import ClusterArrays, PodBatch
+from kubernetes_amd.engine import ClusterArrays, PodBatch, _read_state
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # KSG_ORACLE_LIB: a sanitizer build of the same restatement (tests/test_sanitizers.py)
@@ -50,6 +50,7 @@ def load():
         "orc_schedule_batch": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint32, P(C.c_uint64), vp]),
         "orc_read_requested": (None, [vp, vp, vp]),
         "orc_read_ext_used": (None, [vp, vp]),
+        "orc_read_state": (None, [vp, vp, vp, vp, vp, vp, vp]),
         "orc_admit_pods": (None, [vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_int, vp]),
         "orc_schedule_batch_mt": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint32, P(C.c_uint64), vp, C.c_int]),
         "orc_schedule_batch_mt_ext": (C.c_int, [vp, vp, vp, C.c_uint32, vp, C.c_uint32, P(C.c_uint64), vp, C.c_int]),
@@ -81,6 +82,7 @@ class OracleScheduler:
         self.cfg = cfg
         self._o = C.c_void_p(self._lib.orc_create(C.byref(cfg), 1 if faithful else 0))
         self.n_nodes = 0
+        self.n_services = 0
         self.n_scalar = 0
 
     def close(self):
@@ -101,6 +103,7 @@ class OracleScheduler:
         self._lib.orc_set_cluster(self._o, abi.ptr(nodes), len(nodes), abi.ptr(np_), len(cl.node_pairs),
                                   abi.ptr(pk), len(pk), int(cl.n_services))
         self.n_nodes = len(nodes)
+        self.n_services = int(cl.n_services)
 
     def set_extensions(self, ext: abi.KsgExtConfig):
         self._lib.orc_set_extensions(self._o, C.byref(ext))
@@ -225,6 +228,14 @@ class OracleScheduler:
         m = np.zeros(max(self.n_nodes, 1), np.int64)
         self._lib.orc_read_requested(self._o, abi.ptr(c), abi.ptr(m))
         return c[: self.n_nodes], m[: self.n_nodes]
+
+    def read_state(self) -> dict:
+        """DeviceScheduler.read_state()'s arrays from the restatement's own bookkeeping."""
+        def call(*a):
+            self._lib.orc_read_state(self._o, *a)
+            return abi.KSG_OK
+
+        return _read_state(call, None, int(self.cfg.max_conflict_keys), self.n_services, self.n_nodes)
 
 
 def admit_pods(sets, batch: PodBatch, pairs, mode: int = 3):

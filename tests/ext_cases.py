@@ -11,8 +11,11 @@ from tests.helpers import Case
 
 
 class ExtCase:
-    def __init__(self, name="config2", nn=700, npods=900, seed=11, w_taint=1, w_bal=1, taints=True, gpus=True):
-        self.case = Case(name, nn, npods)
+    def __init__(self, name="config2", nn=700, npods=900, seed=11, w_taint=1, w_bal=1, taints=True, gpus=True,
+                 case=None):
+        """case: a ready Case-shaped object (cfg, view, batch of npods pods on nn nodes) to extend
+        instead of the BASELINE workload `name`."""
+        self.case = case if case is not None else Case(name, nn, npods)
         self.ecfg, node_taints, node_scalar, tols, scal = workload.extension_data(
             nn, npods, seed, taints=taints, gpus=gpus, w_taint=w_taint, w_bal=w_bal)
         self.inter = ExtInterner(self.ecfg)
