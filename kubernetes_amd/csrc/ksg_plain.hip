@@ -187,7 +187,7 @@ __host__ __device__ inline PlLdsOff plain_lds_offsets(uint32_t P, uint32_t nflag
   o.dpos = at;    at += win_al16((size_t)2 * KSG_MAX_SLOTS * 4);
   o.sig = at;     at += win_al16((size_t)2 * KSG_MAX_SLOTS * 4);    // (extension scores) risen slots' scores
   o.cm = at;      at += win_al16((size_t)W * sizeof(PlCommit));
-  o.peer = at;    at += win_al16((size_t)W * 2 * 4);
+  o.peer = at;    at += win_al16((size_t)win_peer_cap(nflag, W) * 2 * 4);
   o.pub = at;     at += win_al16((size_t)((W + 31) / 32) * 4);
   o.drw = at;     at += win_al16((size_t)((W + 31) / 32) * 4);
   o.flag = at;    at += win_al16((size_t)nflag * 4);

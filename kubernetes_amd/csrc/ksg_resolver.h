@@ -133,6 +133,14 @@ struct WinLdsOff {
 
 __host__ __device__ constexpr uint32_t win_al16(size_t x) { return (uint32_t)((x + 15) & ~(size_t)15); }
 
+// (service, node) entries of a window's first-peer list (L_peer): every service of a commit that
+// has no peer yet records one, so a window of W pods records up to KSG_SLOT_SVCS per pod (a pod
+// with more services never commits in a window), and each service at most once (L_peerset:
+// 32 x nflag services)
+__host__ __device__ constexpr uint32_t win_peer_cap(uint32_t nflag, uint32_t W) {
+  return nflag * 32u < W * (uint32_t)KSG_SLOT_SVCS ? nflag * 32u : W * (uint32_t)KSG_SLOT_SVCS;
+}
+
 __host__ __device__ inline WinLdsOff win_lds_offsets(uint32_t P, uint32_t nflag, uint32_t W, bool anti,
                                                      uint32_t dz = 0, uint32_t nsvc = 0) {
   WinLdsOff o;
@@ -154,7 +162,7 @@ __host__ __device__ inline WinLdsOff win_lds_offsets(uint32_t P, uint32_t nflag,
   o.keys = at;    at += win_al16((size_t)KSG_MAX_SLOTS * KSG_SLOT_KEYS * 4);
   o.svcs = at;    at += win_al16((size_t)KSG_MAX_SLOTS * KSG_SLOT_SVCS * 4);
   o.scnt = at;    at += win_al16((size_t)KSG_MAX_SLOTS * KSG_SLOT_SVCS * 4);
-  o.peer = at;    at += win_al16((size_t)W * 2 * 4);
+  o.peer = at;    at += win_al16((size_t)win_peer_cap(nflag, W) * 2 * 4);
   o.out = at;     at += win_al16((size_t)W * 4);
   o.flag = at;    at += win_al16((size_t)nflag * 4);
   o.peerset = at; at += win_al16((size_t)nflag * 4);

@@ -1273,7 +1273,7 @@ __host__ __device__ inline WinLdsOff2 win2_lds_offsets(uint32_t P, uint32_t nfla
   o.r_wp = at;    at += rr ? 0u : win_al16((size_t)R * P * 64 * 2);
   o.dpos = at;    at += rr ? 0u : win_al16((size_t)2 * KSG_MAX_SLOTS * 4);
   o.cm = at;      at += win_al16((size_t)W * sizeof(WinCommit));
-  o.peer = at;    at += win_al16((size_t)W * 2 * 4);
+  o.peer = at;    at += win_al16((size_t)win_peer_cap(nflag, W) * 2 * 4);
   o.pub = at;     at += win_al16((size_t)((W + 31) / 32) * 4);
   o.drw = at;     at += win_al16((size_t)((W + 31) / 32) * 4);
   o.flag = at;    at += win_al16((size_t)nflag * 4);

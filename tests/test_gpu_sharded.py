@@ -141,7 +141,10 @@ def _oracle(name, nn, npods, seed=1234, ext_used=False):
     ("config3", 15000, 50000, 128, 2, 1000), # BASELINE config 3 at full size, 1000-pod batches
     ("config4", 70000, 1000, 128, 2, 500),   # ServiceAntiAffinity, 35k-node shards: the LDS-slot resolver at P = 16
 ] + [(f"fam:{f}", 700, 400, 64, 2, None) for f in ("multi_service", "namespaces", "negative", "big_weights",
-                                                   "existing_hosts", "invalid_selectors")])
+                                                   "existing_hosts", "invalid_selectors")] + [
+    # pods past the window record's limits (tests/families.py LIMIT_FAMILIES): the oversize fallback is a
+    # per-pod scan + exchange + decide between the window rounds, the same number on every rank
+    ("fam:long_lists", 130, 300, 64, 2, None)])
 def test_sharded_batch_matches_oracle(name, nn, npods, window, world, chunk):
     want, st, wc, wm = _oracle(name, nn, npods)
     res = _run(name, nn, npods, window, world=world, chunk=chunk)
@@ -153,6 +156,8 @@ def test_sharded_batch_matches_oracle(name, nn, npods, window, world, chunk):
         assert bad.size == 0, f"rank {rank}: first mismatches at {bad[:8]}: {got[bad[:8]]} vs {want[bad[:8]]}"
         assert rng == st
         assert np.array_equal(np.asarray(uc), wc) and np.array_equal(np.asarray(um), wm)
+        if name == "fam:long_lists":  # (every rank ran windows and counted the fallbacks)
+            assert stats["windows"] > 0 and stats["stops_cache"] > 0, (rank, stats)
     if world == 2 and all(b > a for a, b in spans):
         lo1 = spans[1][0]  # both shards must have produced winners
         assert (want >= lo1).any() and ((want >= 0) & (want < lo1)).any()

@@ -201,6 +201,122 @@ def test_families_ref_model_vs_c_oracle(family):
     assert sum(k == "ok" for k, _ in want) > len(want) // 2
 
 
+_LIMIT_CASES = [("long_lists", 40, "plain"), ("long_lists", 40, "config4"), ("slot_fill", 1, "plain"),
+                ("slot_fill", 3, "plain"), ("slot_fill", 8, "plain"), ("slot_fill", 3, "config4")]
+
+
+@pytest.mark.parametrize("family,nn,policy", _LIMIT_CASES)
+def test_limit_families_ref_model_vs_c_oracle(family, nn, policy):
+    """tests/families.py LIMIT_FAMILIES: id lists at and past the window record's limits, and
+    clusters of 1-8 nodes, under both policies the GPU tests use."""
+    w = families.build(family, nn, 110, policy=policy)
+    want, st_w = _ref_sequence(w, 31)
+    for faithful in (True, False):
+        got, st_g = _c_sequence(w, 31, faithful)
+        bad = [i for i in range(len(want)) if want[i] != got[i]]
+        assert not bad, f"faithful={faithful} first mismatches {[(i, want[i], got[i]) for i in bad[:5]]}"
+        assert st_g == st_w
+    assert sum(k == "ok" for k, _ in want) > len(want) // 2
+    if family == "long_lists":
+        assert [want[i][0] for i in families.LONG_NOFIT] == ["nofit", "nofit"]
+
+
+def test_limit_constants_match_the_headers():
+    import os
+    import re
+
+    csrc = os.path.join(os.path.dirname(abi.__file__), "csrc")
+    text = open(os.path.join(csrc, "ksg_resolver.h")).read() + open(os.path.join(csrc, "ksg_internal.h")).read()
+    got = {k: int(v) for k, v in re.findall(r"#define (KSG_SLOT_KEYS|KSG_SLOT_SVCS|KSG_WIN_INLINE) (\d+)", text)}
+    assert got == {"KSG_SLOT_KEYS": families.SLOT_KEYS, "KSG_SLOT_SVCS": families.SLOT_SVCS,
+                   "KSG_WIN_INLINE": families.WIN_INLINE}
+
+
+def _list_lengths(batch):
+    """-> (conflict keys, services, inline ids) per pod, as the window record counts them."""
+    p = batch.pods
+    nk = p["n_ports"].astype(np.int64) + p["n_pds"]
+    return nk, p["n_svcs"].astype(np.int64), nk + p["n_sel"] + p["n_svcs"]
+
+
+@pytest.mark.parametrize("nn,npods", [(40, 110), (65, 400), (700, 400)])
+def test_long_lists_holds_every_kind_at_its_limit(nn, npods):
+    """The ingested long_lists batch: every kind of families.LONG_KINDS is there, the at-limit
+    kinds exactly at 8 keys / 12 services / 24 inline ids, the others exactly one past one limit
+    and within the other two, the ordinary pods within all three with one-key pods among them."""
+    case = families.FamilyCase("long_lists", nn, npods)
+    nk, ns, inl = _list_lengths(case.batch)
+    seen = {}
+    for i in range(npods):
+        kind = families.long_kind(i)
+        over = (nk[i] > families.SLOT_KEYS, ns[i] > families.SLOT_SVCS, inl[i] > families.WIN_INLINE)
+        if kind is None:
+            assert not any(over) and nk[i] <= 2, i
+            continue
+        seen[kind] = seen.get(kind, 0) + 1
+        want_nk, want_ns, want_inl = families.LONG_KINDS[kind]
+        want_inl += i == families.LONG_NOFIT[1]  # (its one selector pair, which no node carries)
+        assert (ns[i], inl[i]) == (want_ns, want_inl) and (want_nk is None or nk[i] == want_nk), (i, kind)
+        assert any(over) == (kind in families.LONG_PAST), (i, kind)
+    assert set(seen) == set(families.LONG_KINDS) and min(seen.values()) >= 6, seen
+    K, S, I = families.SLOT_KEYS, families.SLOT_SVCS, families.WIN_INLINE
+    kinds = families.LONG_KINDS  # (the exact lengths asserted above, against the limits)
+    assert kinds["ports9"][0] == kinds["ports5_pds4"][0] == K + 1 and kinds["keys8"][0] == K
+    assert kinds["svcs15"][1] > S and kinds["svcs12"][1] == S
+    assert kinds["sel24"][2] == I + 1 and kinds["inline24"][2] == I
+    # sel24 is past the inline record only: the producers' inline flag is false, no slot limit is hit
+    sel24 = [i for i in range(npods) if families.long_kind(i) == "sel24"]
+    assert all(nk[i] == 0 and ns[i] == 1 for i in sel24)
+    p = case.batch.pods
+    assert {int(p["n_ports"][i]) for i in range(npods) if families.long_kind(i) == "ports5_pds4"} == {5}
+    ordinary = [i for i in range(npods) if families.long_kind(i) is None]
+    assert sum(nk[i] >= 1 for i in ordinary) >= len(ordinary) // 3
+    # the two past-limit pods that fit no node: a request no node has, a selector pair no node carries
+    a, b = families.LONG_NOFIT
+    assert families.long_kind(a) == "ports9" and int(p["milli_cpu"][a]) == families.FAT_CPU
+    assert families.long_kind(b) == "svcs15" and int(p["n_sel"][b]) == 1
+    assert int(case.batch.ids[int(p["sel_off"][b])]) == 0  # (pair 0: no node has it)
+    assert int(case.view.arrays.nodes["cap_milli_cpu"].max()) < families.FAT_CPU
+    # every conflict key of a special pod is its own
+    keys = [int(k) for i in range(npods) if families.long_kind(i) for k in
+            list(case.batch.ids[int(p["ports_off"][i]): int(p["ports_off"][i]) + int(p["n_ports"][i])])
+            + list(case.batch.ids[int(p["pds_off"][i]): int(p["pds_off"][i]) + int(p["n_pds"][i])])]
+    assert len(keys) == len(set(keys)) and max(keys) < case.cfg.max_conflict_keys
+
+
+@pytest.mark.parametrize("nn", [1, 2, 3, 8])
+def test_slot_fill_overflows_slots_in_the_reference_placement(nn):
+    """slot_fill has no oversize pod, and the restatement's own placement gives some node more
+    than 8 key entries and more than 12 service entries within every run of 128 pods: a window
+    of 128 cannot resolve them all without a slot overflow."""
+    case = families.FamilyCase("slot_fill", nn, 400)
+    nk, ns, inl = _list_lengths(case.batch)
+    assert nk.max() <= families.SLOT_KEYS and ns.max() <= families.SLOT_SVCS and inl.max() <= families.WIN_INLINE
+    assert (nk >= 1).sum() >= 400 // 3
+    p = case.batch.pods
+    assert 5 <= p["milli_cpu"].min() and p["milli_cpu"].max() <= 11
+    assert 4 << 20 <= p["memory"].min() and p["memory"].max() <= 8 << 20
+    orc = case.load(OracleScheduler(case.cfg))
+    want, _ = orc.batch(case.batch, 777)
+    orc.close()
+    assert (want >= 0).sum() > 200
+    for lo in range(0, 400 - 127, 64):
+        sel = np.flatnonzero(want[lo:lo + 128] >= 0) + lo
+        keys = np.bincount(want[sel], weights=nk[sel], minlength=nn)
+        svcs = np.bincount(want[sel], weights=ns[sel], minlength=nn)
+        assert keys.max() > families.SLOT_KEYS and svcs.max() > families.SLOT_SVCS, (lo, keys, svcs)
+    # the bursts: three pods in a row on one node, any two of them past 8 key entries together,
+    # so that windows of 5 pods meet the overflow as well
+    bursts = {}
+    for i in range(400):
+        if families.fill_burst(i) is not None:
+            bursts.setdefault(families.fill_burst(i), []).append(i)
+    assert len(bursts) == 16
+    for b, (i, j, k) in bursts.items():
+        assert (j, k) == (i + 1, i + 2) and want[i] == want[j] == want[k] >= 0, (b, want[i:k + 1])
+        assert nk[i] == nk[j] == nk[k] == 5 and 2 * 5 > families.SLOT_KEYS
+
+
 @pytest.mark.parametrize("name,nn,npods,threads", [("config2", 700, 1500, 4), ("config1", 500, 1000, 8),
                                                      ("config2", 130, 600, 3)])
 def test_incremental_node_sharded_threads(name, nn, npods, threads):
