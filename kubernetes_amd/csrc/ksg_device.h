@@ -276,9 +276,10 @@ __device__ __forceinline__ void aff_apply_trap(const KsgDev& d, int32_t (&req_af
     if (!((active >> j) & 1u)) req_aff[j] = -1;
 }
 
-template <bool COH = true>
-__device__ __forceinline__ void pod_resolve(const KsgDev& d, const ksg_pod& p, const uint32_t* ids,
-                                            PodCtx& c) {
+// pod_resolve in two parts, for a caller that brings its own service peer
+// (ksg_explain_without.hip). First the pod record's own fields; the spreading terms, which no
+// predicate reads, are 0 until pod_resolve loads them.
+__device__ __forceinline__ void pod_fields(const ksg_pod& p, const uint32_t* ids, PodCtx& c) {
   c.req_cpu = p.milli_cpu;
   c.req_mem = p.memory;
   c.zero_req = (p.milli_cpu == 0 && p.memory == 0);  // predicates.go:129-132
@@ -295,15 +296,13 @@ __device__ __forceinline__ void pod_resolve(const KsgDev& d, const ksg_pod& p, c
   c.svc_total = 0;
   c.ext = nullptr;
   c.ids = ids;
-  int32_t peer = -1;
-  if (c.svc >= 0) {
-    c.spread_max = ld_st<COH>(d.svc_max + c.svc);
-    c.svc_total = ld_st<COH>(d.svc_total + c.svc);
-    peer = ld_st<COH>(d.svc_peer + c.svc);
-  }
-  // ServiceAffinity (predicates.go:257-324): labels the pod's nodeSelector does
-  // not give come from the node of the first service peer.
-  // (loops over KSG_MAX_AFF are fully unrolled so req_aff stays in registers)
+}
+
+// ... then ServiceAffinity (predicates.go:257-324): labels the pod's nodeSelector does
+// not give come from the node of the first service peer (-1 none, -2 a host outside the
+// node list, else the node rank).
+// (loops over KSG_MAX_AFF are fully unrolled so req_aff stays in registers)
+__device__ __forceinline__ void pod_affinity(const KsgDev& d, const ksg_pod& p, int32_t peer, PodCtx& c) {
 #pragma unroll
   for (uint32_t j = 0; j < KSG_MAX_AFF; ++j) c.req_aff[j] = -1;
   if (d.preds & KSG_PRED_SERVICEAFFINITY) {
@@ -328,13 +327,38 @@ __device__ __forceinline__ void pod_resolve(const KsgDev& d, const ksg_pod& p, c
   }
 }
 
+template <bool COH = true>
+__device__ __forceinline__ void pod_resolve(const KsgDev& d, const ksg_pod& p, const uint32_t* ids,
+                                            PodCtx& c) {
+  pod_fields(p, ids, c);
+  int32_t peer = -1;
+  if (c.svc >= 0) {
+    c.spread_max = ld_st<COH>(d.svc_max + c.svc);
+    c.svc_total = ld_st<COH>(d.svc_total + c.svc);
+    peer = ld_st<COH>(d.svc_peer + c.svc);
+  }
+  pod_affinity(d, p, peer, c);
+}
+
+// What a query takes away from the committed state as the predicate walk sees it
+// (ksg_explain_without.hip supplies the real one). This one takes nothing away and compiles
+// to nothing. The hooks: does conflict key `key`, set in the keymap for the lane's node, read
+// as clear; and the node's requested total v of resource k (0 cpu, 1 memory, 2 + r extended
+// resource r) with the absent pods' share subtracted.
+struct KsgNoneAbsent {
+  __device__ __forceinline__ bool key_cleared(uint32_t) const { return false; }
+  __device__ __forceinline__ int64_t used(uint32_t, int64_t v) const { return v; }
+};
+
 // Filter: first failing predicate (fixed order) or 0. wi/bit locate node n in
 // the bitmaps; wi is wave-uniform for the scan kernels. `L` yields the pod's
-// list entries: L.port(i), L.pd(i), L.sel(i).
-template <bool COH, typename L>
+// list entries: L.port(i), L.pd(i), L.sel(i). `absent` is what the query takes away from
+// the node (KsgNoneAbsent: nothing), applied at the two keymap tests and the three reads of
+// a requested total.
+template <bool COH, typename L, typename V = KsgNoneAbsent>
 __device__ __forceinline__ int node_fail_l(const KsgDev& d, const PodCtx& c, const L& lists, uint32_t n,
                                            uint32_t wi, uint64_t bit, int64_t capc, int64_t capm,
-                                           int64_t usedc, int64_t usedm) {
+                                           int64_t usedc, int64_t usedm, const V& absent = V{}) {
   const uint32_t P = d.preds;
   if ((P & KSG_PRED_HOSTNAME) && c.host != -1 && (int32_t)n != c.host) return KSG_FAIL_HOSTNAME;
   if (d.has_static_fit && !(d.static_fit[wi] & bit)) return KSG_FAIL_LABELSPRESENCE;
@@ -344,17 +368,22 @@ __device__ __forceinline__ int node_fail_l(const KsgDev& d, const PodCtx& c, con
   }
   if (P & KSG_PRED_NODISKCONFLICT) {  // NoDiskConflict (predicates.go:73-83)
     for (uint32_t i = 0; i < c.n_pds; ++i)
-      if (ld_st<COH>(d.keymap + (size_t)lists.pd(i) * d.nw + wi) & bit) return KSG_FAIL_NODISKCONFLICT;
+      if ((ld_st<COH>(d.keymap + (size_t)lists.pd(i) * d.nw + wi) & bit) && !absent.key_cleared(lists.pd(i)))
+        return KSG_FAIL_NODISKCONFLICT;
   }
   if (P & KSG_PRED_PODFITSPORTS) {  // PodFitsPorts (predicates.go:326-338)
     for (uint32_t i = 0; i < c.n_ports; ++i)
-      if (ld_st<COH>(d.keymap + (size_t)lists.port(i) * d.nw + wi) & bit) return KSG_FAIL_PODFITSPORTS;
+      if ((ld_st<COH>(d.keymap + (size_t)lists.port(i) * d.nw + wi) & bit) && !absent.key_cleared(lists.port(i)))
+        return KSG_FAIL_PODFITSPORTS;
   }
   if ((P & KSG_PRED_PODFITSRESOURCES) && !c.zero_req) {
     // CheckPodsExceedingCapacity (predicates.go:104-124) over existing+pod, in
     // closed form: every pod fits greedily iff cap==0 || cap - sum(existing) >= req.
-    const bool fc = capc == 0 || (int64_t)((uint64_t)capc - (uint64_t)usedc) >= c.req_cpu;
-    const bool fm = capm == 0 || (int64_t)((uint64_t)capm - (uint64_t)usedm) >= c.req_mem;
+    // (both totals are read before either test: a view that looks something up does so once,
+    // not again on the lanes the first test's short circuit skipped)
+    const int64_t uc = absent.used(0, usedc), um = absent.used(1, usedm);
+    const bool fc = capc == 0 || (int64_t)((uint64_t)capc - (uint64_t)uc) >= c.req_cpu;
+    const bool fm = capm == 0 || (int64_t)((uint64_t)capm - (uint64_t)um) >= c.req_mem;
     if (!(fc && fm)) return KSG_FAIL_PODFITSRESOURCES;
   }
   if (P & KSG_PRED_SERVICEAFFINITY) {
@@ -372,7 +401,7 @@ __device__ __forceinline__ int node_fail_l(const KsgDev& d, const PodCtx& c, con
         const int64_t req = c.ext->scalar[r];
         if (req > 0) {
           const int64_t cap = d.scalar_cap[(size_t)r * d.n_nodes + n];
-          const int64_t used = ld_st<COH>(d.scalar_used + (size_t)r * d.n_nodes + n);
+          const int64_t used = absent.used(2 + r, ld_st<COH>(d.scalar_used + (size_t)r * d.n_nodes + n));
           if (cap < (int64_t)((uint64_t)used + (uint64_t)req)) return KSG_FAIL_SCALAR;
         }
       }
@@ -508,6 +537,81 @@ __device__ __forceinline__ int node_fail(const KsgDev& d, const PodCtx& c, uint3
                                          int64_t usedm) {
   const PtrLists L{c.ports, c.pds, c.sel};
   return node_fail_l<COH>(d, c, L, n, wi, bit, capc, capm, usedc, usedm);
+}
+
+// The explain pass, the body of ksg_explain_kernel and ksg_explain_without_kernel (the tiling
+// and the outputs: ksg_explain.hip's header). `q` says how the query sees a pod and a lane:
+// q.resolve(d, pods, ids, p, c) fills pod p's context, q.touched(wi, bit) whether the lane's
+// node has anything taken away, and q.fail(d, c, p, touched, n, ...) is the lane's fail code
+// for pod p. KsgExplainPlain is ksg_explain_batch's: nothing is taken away.
+struct KsgExplainPlain {
+  __device__ __forceinline__ void resolve(const KsgDev& d, const ksg_pod* pods, const uint32_t* ids, uint32_t p,
+                                          PodCtx& c) const {
+    pod_resolve<false>(d, pods[p], ids, c);
+  }
+  __device__ __forceinline__ bool touched(uint32_t, uint64_t) const { return false; }
+  __device__ __forceinline__ int fail(const KsgDev& d, const PodCtx& c, uint32_t, bool, uint32_t n, uint32_t wi,
+                                      uint64_t bit, int64_t capc, int64_t capm, int64_t usedc, int64_t usedm) const {
+    return node_fail<false>(d, c, n, wi, bit, capc, capm, usedc, usedm);
+  }
+};
+
+#define KSG_EXPLAIN_WAVES (KSG_EXPLAIN_TILE / 64)
+static_assert(KSG_EXPLAIN_TILE % 64 == 0, "one bitmap word per wave");
+static_assert((KSG_EXPLAIN_SLOTS & (KSG_EXPLAIN_SLOTS - 1)) == 0 && KSG_FAIL_SCALAR < KSG_EXPLAIN_SLOTS,
+              "histogram slots: a power of two past the last fail code");
+
+template <typename Q>
+__device__ __forceinline__ void ksg_explain_pass(const KsgDev& d, const Q& q, const ksg_pod* pods,
+                                                 const ksg_pod_ext* exts, const uint32_t* ids,
+                                                 uint32_t n_pods, uint8_t* codes, uint32_t* hist,
+                                                 uint8_t* err) {
+  __shared__ uint32_t s_hist[KSG_EXPLAIN_CHUNK * KSG_EXPLAIN_SLOTS];
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  const uint32_t wi = blockIdx.x * KSG_EXPLAIN_WAVES + (tid >> 6);  // wave-uniform
+  const uint32_t n = wi * 64 + lane;
+  const uint64_t bit = 1ULL << lane;
+  const bool valid = wi < d.nw && n < d.n_nodes;  // the last word's tail neither stores nor counts
+  const uint32_t p0 = blockIdx.y * KSG_EXPLAIN_CHUNK;
+  const uint32_t p1 = min(p0 + (uint32_t)KSG_EXPLAIN_CHUNK, n_pods);
+  for (uint32_t i = tid; i < KSG_EXPLAIN_CHUNK * KSG_EXPLAIN_SLOTS; i += KSG_EXPLAIN_TILE) s_hist[i] = 0;
+  int64_t capc = 0, capm = 0, usedc = 0, usedm = 0;
+  bool touched = false;
+  if (valid) {
+    capc = d.cap_cpu[n];
+    capm = d.cap_mem[n];
+    usedc = d.used_cpu[n];
+    usedm = d.used_mem[n];
+    touched = q.touched(wi, bit);
+  }
+  __syncthreads();
+  if (wi < d.nw) {  // (a whole wave past the last word only joins the barriers)
+    const uint64_t live = __ballot(valid);
+    for (uint32_t p = p0; p < p1; ++p) {
+      PodCtx c;
+      q.resolve(d, pods, ids, p, c);
+      if (exts) c.ext = exts + p;
+      if (blockIdx.x == 0 && tid == 0) err[p] = c.error ? 1 : 0;
+      if (c.error) {  // wave-uniform: the rows stay zero
+        if (codes && valid) codes[(size_t)p * d.n_nodes + n] = 0;
+        continue;
+      }
+      // (node_fail's extended-resource loads are indexed by n: only for a lane with a node)
+      const int code =
+          valid ? (q.fail(d, c, p, touched, n, wi, bit, capc, capm, usedc, usedm) & (KSG_EXPLAIN_SLOTS - 1)) : 0;
+      if (codes && valid) codes[(size_t)p * d.n_nodes + n] = (uint8_t)code;
+      uint64_t rem = live;
+      while (rem) {  // one ballot per distinct code present
+        const int cc = __builtin_amdgcn_readlane(code, (int)__builtin_ctzll(rem));
+        const uint64_t m = __ballot(valid && code == cc);
+        if (lane == 0) atomicAdd(&s_hist[(p - p0) * KSG_EXPLAIN_SLOTS + cc], (uint32_t)__popcll(m));
+        rem &= ~m;
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t i = tid; i < (p1 - p0) * KSG_EXPLAIN_SLOTS; i += KSG_EXPLAIN_TILE)
+    if (s_hist[i]) atomicAdd(hist + (size_t)p0 * KSG_EXPLAIN_SLOTS + i, s_hist[i]);
 }
 
 // Priorities without ServiceAntiAffinity (added after the domain counts).

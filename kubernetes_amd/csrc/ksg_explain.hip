@@ -23,60 +23,13 @@
 #include "ksg_device.h"
 #include "ksg_launch.h"
 
-#define KSG_EXPLAIN_WAVES (KSG_EXPLAIN_TILE / 64)
-static_assert(KSG_EXPLAIN_TILE % 64 == 0, "one bitmap word per wave");
-static_assert((KSG_EXPLAIN_SLOTS & (KSG_EXPLAIN_SLOTS - 1)) == 0 && KSG_FAIL_SCALAR < KSG_EXPLAIN_SLOTS,
-              "histogram slots: a power of two past the last fail code");
-
 __global__ __launch_bounds__(KSG_EXPLAIN_TILE) void ksg_explain_kernel(KsgDev d, const ksg_pod* __restrict__ pods,
                                                                       const ksg_pod_ext* __restrict__ exts,
                                                                       const uint32_t* __restrict__ ids, uint32_t n_pods,
                                                                       uint8_t* __restrict__ codes,
                                                                       uint32_t* __restrict__ hist,
                                                                       uint8_t* __restrict__ err) {
-  __shared__ uint32_t s_hist[KSG_EXPLAIN_CHUNK * KSG_EXPLAIN_SLOTS];
-  const uint32_t tid = threadIdx.x, lane = tid & 63;
-  const uint32_t wi = blockIdx.x * KSG_EXPLAIN_WAVES + (tid >> 6);  // wave-uniform
-  const uint32_t n = wi * 64 + lane;
-  const uint64_t bit = 1ULL << lane;
-  const bool valid = wi < d.nw && n < d.n_nodes;  // the last word's tail neither stores nor counts
-  const uint32_t p0 = blockIdx.y * KSG_EXPLAIN_CHUNK;
-  const uint32_t p1 = min(p0 + (uint32_t)KSG_EXPLAIN_CHUNK, n_pods);
-  for (uint32_t i = tid; i < KSG_EXPLAIN_CHUNK * KSG_EXPLAIN_SLOTS; i += KSG_EXPLAIN_TILE) s_hist[i] = 0;
-  int64_t capc = 0, capm = 0, usedc = 0, usedm = 0;
-  if (valid) {
-    capc = d.cap_cpu[n];
-    capm = d.cap_mem[n];
-    usedc = d.used_cpu[n];
-    usedm = d.used_mem[n];
-  }
-  __syncthreads();
-  if (wi < d.nw) {  // (a whole wave past the last word only joins the barriers)
-    const uint64_t live = __ballot(valid);
-    for (uint32_t p = p0; p < p1; ++p) {
-      PodCtx c;
-      pod_resolve<false>(d, pods[p], ids, c);
-      if (exts) c.ext = exts + p;
-      if (blockIdx.x == 0 && tid == 0) err[p] = c.error ? 1 : 0;
-      if (c.error) {  // wave-uniform: the rows stay zero
-        if (codes && valid) codes[(size_t)p * d.n_nodes + n] = 0;
-        continue;
-      }
-      // (node_fail's extended-resource loads are indexed by n: only for a lane with a node)
-      const int code = valid ? (node_fail<false>(d, c, n, wi, bit, capc, capm, usedc, usedm) & (KSG_EXPLAIN_SLOTS - 1)) : 0;
-      if (codes && valid) codes[(size_t)p * d.n_nodes + n] = (uint8_t)code;
-      uint64_t rem = live;
-      while (rem) {  // one ballot per distinct code present
-        const int cc = __builtin_amdgcn_readlane(code, (int)__builtin_ctzll(rem));
-        const uint64_t m = __ballot(valid && code == cc);
-        if (lane == 0) atomicAdd(&s_hist[(p - p0) * KSG_EXPLAIN_SLOTS + cc], (uint32_t)__popcll(m));
-        rem &= ~m;
-      }
-    }
-  }
-  __syncthreads();
-  for (uint32_t i = tid; i < (p1 - p0) * KSG_EXPLAIN_SLOTS; i += KSG_EXPLAIN_TILE)
-    if (s_hist[i]) atomicAdd(hist + (size_t)p0 * KSG_EXPLAIN_SLOTS + i, s_hist[i]);
+  ksg_explain_pass(d, KsgExplainPlain{}, pods, exts, ids, n_pods, codes, hist, err);
 }
 
 // codes: optional (nullptr: no per-node bytes); hist zeroed by the caller; grid.y covers n_pods

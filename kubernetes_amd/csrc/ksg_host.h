@@ -1,6 +1,7 @@
 // ksg_host.h — what the host translation units share: the context (struct ksg_ctx), the
 // owning scratch-buffer types, the error macros, the environment switches' parsers and the
-// helpers ksg_runtime.cpp defines and ksg_batch.cpp calls.
+// helpers ksg_runtime.cpp defines and ksg_batch.cpp and ksg_without.cpp call, among them the
+// frame of the read-only batch queries (query_enter ... query_chunks).
 #ifndef KSG_HOST_H_
 #define KSG_HOST_H_
 
@@ -11,6 +12,7 @@
 #include <array>
 #include <chrono>
 #include <cstdlib>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -373,7 +375,7 @@ struct ksg_ctx {
 
 #define KSG_LOCK(c) std::lock_guard<std::recursive_mutex> ksg_lock_((c)->mu)
 
-// ---- ksg_runtime.cpp's helpers the batch driver (ksg_batch.cpp) calls -----------
+// ---- ksg_runtime.cpp's helpers the other host files call --------------------------
 #pragma GCC visibility push(hidden)
 
 enum class Reduce { Sum, Max };
@@ -393,6 +395,41 @@ int allgather(ksg_ctx* c, const void* dsend, void* drecv, size_t bytes);
 int allreduce_i32(ksg_ctx* c, Reduce op, const int32_t* dsend, int32_t* drecv, uint32_t n);
 bool anti_on(const ksg_ctx* c);
 uint8_t* rec_buf(ksg_ctx* c);
+
+// ---- the read-only batch queries' frame -------------------------------------------
+// ksg_explain_batch, ksg_prioritize_batch, ksg_headroom_batch (ksg_runtime.cpp) and
+// ksg_explain_without (ksg_without.cpp) answer for n pods against the device state as it
+// stands, in one or more launches over chunks of pods. Each is: its null-pointer check, the
+// lock, its own argument checks, then these steps in this order, with what only it does
+// (buffers, zeroing, tables, where the results land) in between. Every step returns a KSG_*
+// code the entry point passes on.
+//
+// enter: ksg_evaluate's protocol (no pending begin, no records while extensions are off, the
+// server leaves the stream, the mirror and the cluster are current, the device is set), then
+// *last_ms = 0, then n == 0 -> kQueryDone (nothing to do: the entry point returns KSG_OK),
+// no nodes -> KSG_NONODES, ids missing. Any other non-zero code the entry point returns as it is.
+constexpr int kQueryDone = 1 << 20;  // (no KSG_* code)
+int query_enter(ksg_ctx* c, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids, uint32_t n_ids, double* last_ms);
+// validate: ksg_schedule_batch's checks pod by pod; also(i), where given, after pod i's own
+// checks and before pod i + 1's. No uid is looked at and note_requests is NOT called.
+int query_validate(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
+                   uint32_t n_ids, const std::function<int(uint32_t)>& also = {});
+// upload: the patches, the pods and their ids, and the extension records into d_pext. *dext is
+// nullptr without records (the kernels then skip the extension filters, as an all-zero record
+// passes them), unless zero_records asks for all-zero ones whenever the extensions are on.
+int query_upload(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
+                 uint32_t n_ids, bool zero_records, const ksg_pod_ext** dext);
+// pods per launch: as many as `budget` bytes of staging hold at bytes_per_pod each (0: no
+// staging, no bound), at most 2^20, whole pod chunks of the kernel past one chunk, at least 1
+// and at most n.
+uint32_t query_per(size_t budget, size_t bytes_per_pod, uint32_t chunk, uint32_t n);
+// the chunk loop: for each chunk [a, a + m) of `per` pods launch(a, m) between the events
+// ev_x0 / ev_x1 (created here on first use), then copies(a, m, last) outside them, which
+// enqueues the chunk's per-node rows and with the last chunk the per-pod results, then one
+// stream synchronise; the elapsed times add up in *last_ms. (Callers pass their lambdas as
+// std::cref: a std::function holding a reference allocates nothing.)
+int query_chunks(ksg_ctx* c, uint32_t n, uint32_t per, double* last_ms, const std::function<int(uint32_t, uint32_t)>& launch,
+                 const std::function<int(uint32_t, uint32_t, bool)>& copies);
 extern "C" {  // (defined among the entry points, inside ksg_runtime.cpp's extern "C" block)
 int remove_pod_impl(ksg_ctx* c, uint64_t uid);
 int note_ext(ksg_ctx* c, const ksg_pod* p, const ksg_pod_ext* e, size_t n_ids);

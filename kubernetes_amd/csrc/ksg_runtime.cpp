@@ -787,6 +787,74 @@ bool srv_put_pod(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, size_t n_i
   return true;
 }
 
+// ---- the read-only batch queries' frame (ksg_host.h) --------------------------
+int query_enter(ksg_ctx* c, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids, uint32_t n_ids, double* last_ms) {
+  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
+  if (ext && !c->ext_on) return fail(c, KSG_ERR_STATE, "extensions are off");
+  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
+  if (int rc0 = flush_deferred(c)) return rc0;  // (the mirror now holds the last batch)
+  if (int rs = cluster_ok(c)) return rs;
+  HIPCHK(c, hipSetDevice(c->device));
+  *last_ms = 0.0;
+  if (n == 0) return kQueryDone;
+  if (c->N == 0) return KSG_NONODES;
+  if (n_ids && !ids) return fail(c, KSG_ERR_ARG, "ids missing");
+  return KSG_OK;
+}
+
+int query_validate(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
+                   uint32_t n_ids, const std::function<int(uint32_t)>& also) {
+  int rc;
+  for (uint32_t i = 0; i < n; ++i) {
+    if ((rc = check_pod(c, pods + i, ids, n_ids))) return rc;
+    if (ext && ((rc = check_ext_range(c, ext + i, n_ids)) || (rc = check_taint_ids(c, ext + i, ids)))) return rc;
+    if (also && (rc = also(i))) return rc;
+  }
+  return KSG_OK;
+}
+
+int query_upload(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
+                 uint32_t n_ids, bool zero_records, const ksg_pod_ext** dext) {
+  int rc;
+  *dext = nullptr;
+  if ((rc = flush_patches(c))) return rc;
+  if ((rc = upload_pods(c, pods, n, ids, n_ids))) return rc;
+  if (!(ext || (zero_records && c->ext_on))) return KSG_OK;
+  if ((rc = c->d_pext.grow(c, n))) return rc;
+  if (ext) HIPCHK(c, hipMemcpyAsync(c->d_pext, ext, (size_t)n * sizeof(ksg_pod_ext), hipMemcpyHostToDevice, c->st));
+  else HIPCHK(c, hipMemsetAsync(c->d_pext, 0, (size_t)n * sizeof(ksg_pod_ext), c->st));
+  *dext = c->d_pext;
+  return KSG_OK;
+}
+
+uint32_t query_per(size_t budget, size_t bytes_per_pod, uint32_t chunk, uint32_t n) {
+  uint32_t per = 1u << 20;  // (the grid's y extent stays far below 65,535)
+  if (bytes_per_pod) per = (uint32_t)std::min<size_t>(per, std::max<size_t>(budget / bytes_per_pod, 1));
+  if (per > chunk) per -= per % chunk;
+  return std::min(per, n);
+}
+
+int query_chunks(ksg_ctx* c, uint32_t n, uint32_t per, double* last_ms, const std::function<int(uint32_t, uint32_t)>& launch,
+                 const std::function<int(uint32_t, uint32_t, bool)>& copies) {
+  int rc;
+  if (!c->ev_x0) {
+    HIPCHK(c, hipEventCreate(&c->ev_x0));
+    HIPCHK(c, hipEventCreate(&c->ev_x1));
+  }
+  for (uint32_t a = 0; a < n; a += per) {
+    const uint32_t m = std::min(per, n - a);
+    HIPCHK(c, hipEventRecord(c->ev_x0, c->st));
+    if ((rc = launch(a, m))) return rc;
+    HIPCHK(c, hipEventRecord(c->ev_x1, c->st));
+    if ((rc = copies(a, m, a + per >= n))) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->st));  // (the staging buffers are reused by the next chunk)
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_x0, c->ev_x1));
+    *last_ms += ms;
+  }
+  return KSG_OK;
+}
+
 #pragma GCC visibility pop
 
 extern "C" {
@@ -1960,74 +2028,45 @@ int ksg_evaluate_ext(ksg_ctx* c, const ksg_pod* pod, const ksg_pod_ext* ext, con
   return rc;
 }
 
-// FitError reports for many pods: one grid-wide pass (ksg_explain.hip) over the device state as
-// it stands. The protocol is ksg_evaluate's (lock, no pending begin, the server leaves the stream,
-// the mirror and the patches are flushed), the validation ksg_schedule_batch's; no uid is looked
-// at and note_requests is NOT called: no score is computed, so a pod's requests need not turn the
-// context to the int64 kernels, and later batches take the path they would have taken.
+// The read-only batch queries, each on the frame ksg_host.h describes (query_enter ...
+// query_chunks). None looks at a uid or calls note_requests: no query turns the context to the
+// int64 kernels, and later batches take the path they would have taken. A sharded context
+// covers the whole (replicated) cluster alone.
+
+// FitError reports for many pods: one grid-wide pass (ksg_explain.hip) per chunk.
 int ksg_explain_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
                       uint32_t n_ids, uint8_t* codes, uint32_t* hist, uint8_t* err) {
   if (!c || (n && (!pods || !hist || !err))) return KSG_ERR_ARG;
   KSG_LOCK(c);
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
-  if (ext && !c->ext_on) return fail(c, KSG_ERR_STATE, "extensions are off");
-  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
-  if (int rc0 = flush_deferred(c)) return rc0;
-  if (int rs = cluster_ok(c)) return rs;
-  HIPCHK(c, hipSetDevice(c->device));
-  c->last_explain_ms = 0.0;
-  if (n == 0) return KSG_OK;
-  if (c->N == 0) return KSG_NONODES;
-  if (n_ids && !ids) return fail(c, KSG_ERR_ARG, "ids missing");
   int rc;
-  for (uint32_t i = 0; i < n; ++i) {
-    if ((rc = check_pod(c, pods + i, ids, n_ids))) return rc;
-    if (ext && ((rc = check_ext_range(c, ext + i, n_ids)) || (rc = check_taint_ids(c, ext + i, ids)))) return rc;
-  }
-  if ((rc = flush_patches(c))) return rc;
-  if ((rc = upload_pods(c, pods, n, ids, n_ids))) return rc;
-  const ksg_pod_ext* dext = nullptr;
-  if (ext) {  // (no record: node_fail skips the extension filters, as an all-zero record passes them)
-    if ((rc = c->d_pext.grow(c, n))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_pext, ext, (size_t)n * sizeof(ksg_pod_ext), hipMemcpyHostToDevice, c->st));
-    dext = c->d_pext;
-  }
+  if ((rc = query_enter(c, ext, n, ids, n_ids, &c->last_explain_ms))) return rc == kQueryDone ? KSG_OK : rc;
+  if ((rc = query_validate(c, pods, ext, n, ids, n_ids))) return rc;
+  const ksg_pod_ext* dext;
+  if ((rc = query_upload(c, pods, ext, n, ids, n_ids, false, &dext))) return rc;
   // hist and err for the whole call; the per-node codes in a bounded staging buffer, a chunk
-  // of pods at a time (whole pod chunks of the kernel, at least one pod)
+  // of pods at a time
   const size_t hb = (size_t)n * KSG_EXPLAIN_SLOTS * sizeof(uint32_t);
   if ((rc = c->d_xhist.grow(c, hb + n))) return rc;
   uint32_t* d_hist = reinterpret_cast<uint32_t*>(c->d_xhist.p);
   uint8_t* d_err = c->d_xhist + hb;
   HIPCHK(c, hipMemsetAsync(c->d_xhist, 0, hb + n, c->st));
-  uint32_t per = 1u << 20;  // pods per launch (the grid's y extent stays far below 65,535)
-  if (codes) {
-    per = (uint32_t)std::min<size_t>(per, std::max<size_t>(kExplainStageBytes / c->N, 1));
-    if (per > KSG_EXPLAIN_CHUNK) per -= per % KSG_EXPLAIN_CHUNK;
-    per = std::min(per, n);
-    if ((rc = c->d_xcodes.grow(c, (size_t)per * c->N))) return rc;
-  }
-  if (!c->ev_x0) {
-    HIPCHK(c, hipEventCreate(&c->ev_x0));
-    HIPCHK(c, hipEventCreate(&c->ev_x1));
-  }
-  for (uint32_t a = 0; a < n; a += per) {
-    const uint32_t m = std::min(per, n - a);
-    HIPCHK(c, hipEventRecord(c->ev_x0, c->st));
+  const uint32_t per = query_per(kExplainStageBytes, codes ? c->N : 0, KSG_EXPLAIN_CHUNK, n);
+  if (codes && (rc = c->d_xcodes.grow(c, (size_t)per * c->N))) return rc;
+  const auto launch = [&](uint32_t a, uint32_t m) {
     HIPCHK(c, ksg_launch_explain(c->dev, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m,
                                  codes ? c->d_xcodes : nullptr, d_hist + (size_t)a * KSG_EXPLAIN_SLOTS, d_err + a, c->st));
-    HIPCHK(c, hipEventRecord(c->ev_x1, c->st));
+    return KSG_OK;
+  };
+  const auto copies = [&](uint32_t a, uint32_t m, bool last) {
     if (codes)
       HIPCHK(c, hipMemcpyAsync(codes + (size_t)a * c->N, c->d_xcodes, (size_t)m * c->N, hipMemcpyDeviceToHost, c->st));
-    if (a + per >= n) {  // the last chunk's wait also brings hist and err back
+    if (last) {  // straight into the caller's arrays
       HIPCHK(c, hipMemcpyAsync(hist, d_hist, hb, hipMemcpyDeviceToHost, c->st));
       HIPCHK(c, hipMemcpyAsync(err, d_err, n, hipMemcpyDeviceToHost, c->st));
     }
-    HIPCHK(c, hipStreamSynchronize(c->st));  // (the staging buffer is reused by the next chunk)
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_x0, c->ev_x1));
-    c->last_explain_ms += ms;
-  }
-  return KSG_OK;
+    return KSG_OK;
+  };
+  return query_chunks(c, n, per, &c->last_explain_ms, std::cref(launch), std::cref(copies));
 }
 
 int ksg_last_explain_ms(ksg_ctx* c, double* ms) {
@@ -2038,9 +2077,7 @@ int ksg_last_explain_ms(ksg_ctx* c, double* ms) {
 }
 
 // Ranked hosts for many pods: the grid-wide reduce / score / merge passes of ksg_prioritize.hip
-// over the device state as it stands. Protocol and validation are ksg_explain_batch's. Scores
-// are always wrapping int64, so note_requests is NOT called and later batches take the path
-// they would have taken. A sharded context covers the whole (replicated) cluster alone.
+// per chunk. Scores are always wrapping int64.
 int ksg_prioritize_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
                          uint32_t n_ids, uint32_t top, int64_t* max_score, uint32_t* tie_count, uint32_t* fit_count,
                          int32_t* top_nodes, int64_t* top_scores, int64_t* scores, uint8_t* err) {
@@ -2048,30 +2085,11 @@ int ksg_prioritize_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext
   KSG_LOCK(c);
   if (top > KSG_PRIO_MAX_TOP) return fail(c, KSG_ERR_ARG, "top %u > KSG_PRIO_MAX_TOP", top);
   if (n && top && (!top_nodes || !top_scores)) return fail(c, KSG_ERR_ARG, "top > 0 needs top_nodes and top_scores");
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
-  if (ext && !c->ext_on) return fail(c, KSG_ERR_STATE, "extensions are off");
-  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
-  if (int rc0 = flush_deferred(c)) return rc0;
-  if (int rs = cluster_ok(c)) return rs;
-  HIPCHK(c, hipSetDevice(c->device));
-  c->last_prioritize_ms = 0.0;
-  if (n == 0) return KSG_OK;
-  if (c->N == 0) return KSG_NONODES;
-  if (n_ids && !ids) return fail(c, KSG_ERR_ARG, "ids missing");
   int rc;
-  for (uint32_t i = 0; i < n; ++i) {
-    if ((rc = check_pod(c, pods + i, ids, n_ids))) return rc;
-    if (ext && ((rc = check_ext_range(c, ext + i, n_ids)) || (rc = check_taint_ids(c, ext + i, ids)))) return rc;
-  }
-  if ((rc = flush_patches(c))) return rc;
-  if ((rc = upload_pods(c, pods, n, ids, n_ids))) return rc;
-  const ksg_pod_ext* dext = nullptr;
-  if (c->ext_on) {  // (no records: all-zero ones, which is what ksg_evaluate scores a plain pod with)
-    if ((rc = c->d_pext.grow(c, n))) return rc;
-    if (ext) HIPCHK(c, hipMemcpyAsync(c->d_pext, ext, (size_t)n * sizeof(ksg_pod_ext), hipMemcpyHostToDevice, c->st));
-    else HIPCHK(c, hipMemsetAsync(c->d_pext, 0, (size_t)n * sizeof(ksg_pod_ext), c->st));
-    dext = c->d_pext;
-  }
+  if ((rc = query_enter(c, ext, n, ids, n_ids, &c->last_prioritize_ms))) return rc == kQueryDone ? KSG_OK : rc;
+  if ((rc = query_validate(c, pods, ext, n, ids, n_ids))) return rc;
+  const ksg_pod_ext* dext;  // (no records: all-zero ones, which is what ksg_evaluate scores a plain pod with)
+  if ((rc = query_upload(c, pods, ext, n, ids, n_ids, true, &dext))) return rc;
   // the per-pod results of the whole call: int64 max[n], int64 top_scores[n][top], uint32 ties[n],
   // uint32 fit[n], int32 top_nodes[n][top], uint8 err[n]
   const size_t o_ts = (size_t)n * 8, o_tie = o_ts + (size_t)n * top * 8, o_fit = o_tie + (size_t)n * 4;
@@ -2079,13 +2097,10 @@ int ksg_prioritize_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext
   if ((rc = c->d_pout.grow(c, ob)) || (rc = c->h_dn.grow(c, ob))) return rc;
   uint8_t* const po = c->d_pout;
   // pods per launch: the normalised terms, tile partials and candidates of a chunk, and its
-  // per-node scores, each within the staging budget (whole pod chunks of the kernels, >= 1 pod)
+  // per-node scores where asked for, each within the staging budget
   const size_t T = (c->nw + KSG_PRIO_WAVES - 1) / KSG_PRIO_WAVES, D1 = (size_t)c->dev.n_domains_total + 1;
   const size_t bpp = D1 * 4 + T * (sizeof(KsgPrioPart) + (size_t)top * 12);
-  uint32_t per = (uint32_t)std::min<size_t>(1u << 20, std::max<size_t>(kExplainStageBytes / bpp, 1));
-  if (scores) per = (uint32_t)std::min<size_t>(per, std::max<size_t>(kExplainStageBytes / ((size_t)c->N * 8), 1));
-  if (per > KSG_EXPLAIN_CHUNK) per -= per % KSG_EXPLAIN_CHUNK;
-  per = std::min(per, n);
+  const uint32_t per = query_per(kExplainStageBytes, scores ? std::max(bpp, (size_t)c->N * 8) : bpp, KSG_EXPLAIN_CHUNK, n);
   const size_t o_part = ((size_t)per * D1 * 4 + 15) & ~(size_t)15, o_cs = o_part + (size_t)per * T * sizeof(KsgPrioPart);
   const size_t o_cn = o_cs + (size_t)per * T * top * 8;
   if ((rc = c->d_ppart.grow(c, o_cn + (size_t)per * T * top * 4))) return rc;
@@ -2095,32 +2110,26 @@ int ksg_prioritize_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext
   int64_t* const cs = reinterpret_cast<int64_t*>(c->d_ppart + o_cs);
   int32_t* const cn = reinterpret_cast<int32_t*>(c->d_ppart + o_cn);
   const bool reduce = ksg_prio_needs_reduce(c->dev, ext != nullptr);
-  if (!c->ev_x0) {
-    HIPCHK(c, hipEventCreate(&c->ev_x0));
-    HIPCHK(c, hipEventCreate(&c->ev_x1));
-  }
-  for (uint32_t a = 0; a < n; a += per) {
-    const uint32_t m = std::min(per, n - a);
+  const auto launch = [&](uint32_t a, uint32_t m) {
     const ksg_pod_ext* xa = dext ? dext + a : nullptr;
-    HIPCHK(c, hipEventRecord(c->ev_x0, c->st));
     HIPCHK(c, hipMemsetAsync(dnorm, 0, (size_t)m * D1 * 4, c->st));
     if (reduce) HIPCHK(c, ksg_launch_prio_reduce(c->dev, c->d_pods + a, xa, c->d_ids, m, dnorm, c->st));
-    HIPCHK(c, ksg_launch_prio_score(c->dev, c->d_pods + a, xa, c->d_ids, m, top, dnorm, scores ? c->d_pscores.p : nullptr,
-                                    part, cs, cn, po + o_err + a, c->st));
+    HIPCHK(c, ksg_launch_prio_score(c->dev, c->d_pods + a, xa, c->d_ids, m, top, dnorm,
+                                    scores ? c->d_pscores.p : nullptr, part, cs, cn, po + o_err + a, c->st));
     HIPCHK(c, ksg_launch_prio_merge(c->dev, m, top, part, cs, cn, reinterpret_cast<int64_t*>(po) + a,
                                     reinterpret_cast<uint32_t*>(po + o_tie) + a, reinterpret_cast<uint32_t*>(po + o_fit) + a,
                                     reinterpret_cast<int32_t*>(po + o_tn) + (size_t)a * top,
                                     reinterpret_cast<int64_t*>(po + o_ts) + (size_t)a * top, c->st));
-    HIPCHK(c, hipEventRecord(c->ev_x1, c->st));
+    return KSG_OK;
+  };
+  const auto copies = [&](uint32_t a, uint32_t m, bool last) {
     if (scores)
       HIPCHK(c, hipMemcpyAsync(scores + (size_t)a * c->N, c->d_pscores, (size_t)m * c->N * 8, hipMemcpyDeviceToHost, c->st));
-    if (a + per >= n)  // the last chunk's wait also brings the per-pod results back
-      HIPCHK(c, hipMemcpyAsync(c->h_dn, po, ob, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));  // (the staging buffers are reused by the next chunk)
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_x0, c->ev_x1));
-    c->last_prioritize_ms += ms;
-  }
+    if (last) HIPCHK(c, hipMemcpyAsync(c->h_dn, po, ob, hipMemcpyDeviceToHost, c->st));
+    return KSG_OK;
+  };
+  rc = query_chunks(c, n, per, &c->last_prioritize_ms, std::cref(launch), std::cref(copies));
+  if (rc) return rc;
   memcpy(max_score, c->h_dn, (size_t)n * 8);
   memcpy(tie_count, c->h_dn + o_tie, (size_t)n * 4);
   memcpy(fit_count, c->h_dn + o_fit, (size_t)n * 4);
@@ -2139,77 +2148,46 @@ int ksg_last_prioritize_ms(ksg_ctx* c, double* ms) {
   return KSG_OK;
 }
 
-// How many copies of each pod every node can take: one grid-wide pass (ksg_headroom.hip) over
-// the device state as it stands. Protocol and validation are ksg_explain_batch's; no uid is
-// looked at and note_requests is NOT called (no score is computed), so later batches take the
-// path they would have taken. A sharded context covers the whole (replicated) cluster alone.
+// How many copies of each pod every node can take: one grid-wide pass (ksg_headroom.hip) per
+// chunk.
 int ksg_headroom_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
                        uint32_t n_ids, uint32_t limit, uint64_t* total, uint32_t* fit_count, uint32_t* max_count,
                        uint32_t* bind_hist, uint32_t* counts, uint8_t* err) {
   if (!c || (n && (!pods || !total || !fit_count || !max_count || !bind_hist || !err))) return KSG_ERR_ARG;
   KSG_LOCK(c);
   if (limit == 0) return fail(c, KSG_ERR_ARG, "limit 0");
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
-  if (ext && !c->ext_on) return fail(c, KSG_ERR_STATE, "extensions are off");
-  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
-  if (int rc0 = flush_deferred(c)) return rc0;
-  if (int rs = cluster_ok(c)) return rs;
-  HIPCHK(c, hipSetDevice(c->device));
-  c->last_headroom_ms = 0.0;
-  if (n == 0) return KSG_OK;
-  if (c->N == 0) return KSG_NONODES;
-  if (n_ids && !ids) return fail(c, KSG_ERR_ARG, "ids missing");
   int rc;
-  for (uint32_t i = 0; i < n; ++i) {
-    if ((rc = check_pod(c, pods + i, ids, n_ids))) return rc;
-    if (ext && ((rc = check_ext_range(c, ext + i, n_ids)) || (rc = check_taint_ids(c, ext + i, ids)))) return rc;
-  }
-  if ((rc = flush_patches(c))) return rc;
-  if ((rc = upload_pods(c, pods, n, ids, n_ids))) return rc;
-  const ksg_pod_ext* dext = nullptr;
-  if (ext) {  // (no record: node_fail and node_room skip the extension filters, as an all-zero record passes them)
-    if ((rc = c->d_pext.grow(c, n))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_pext, ext, (size_t)n * sizeof(ksg_pod_ext), hipMemcpyHostToDevice, c->st));
-    dext = c->d_pext;
-  }
+  if ((rc = query_enter(c, ext, n, ids, n_ids, &c->last_headroom_ms))) return rc == kQueryDone ? KSG_OK : rc;
+  if ((rc = query_validate(c, pods, ext, n, ids, n_ids))) return rc;
+  const ksg_pod_ext* dext;
+  if ((rc = query_upload(c, pods, ext, n, ids, n_ids, false, &dext))) return rc;
   // the per-pod results of the whole call: uint64 total[n], uint32 max[n], uint32 fit[n],
   // uint32 hist[n][KSG_HEADROOM_SLOTS], uint8 err[n]; the per-node counts in a bounded staging
-  // buffer, a chunk of pods at a time (whole pod chunks of the kernel, at least one pod)
+  // buffer, a chunk of pods at a time
   const size_t o_max = (size_t)n * 8, o_fit = o_max + (size_t)n * 4, o_hist = o_fit + (size_t)n * 4;
   const size_t hb = (size_t)n * KSG_HEADROOM_SLOTS * sizeof(uint32_t), o_err = o_hist + hb, ob = o_err + n;
   if ((rc = c->d_hout.grow(c, ob)) || (rc = c->h_dn.grow(c, ob))) return rc;
   uint8_t* const ho = c->d_hout;
   HIPCHK(c, hipMemsetAsync(ho, 0, ob, c->st));
-  uint32_t per = 1u << 20;  // pods per launch (the grid's y extent stays far below 65,535)
-  if (counts) {
-    per = (uint32_t)std::min<size_t>(per, std::max<size_t>(c->headroom_stage / ((size_t)c->N * sizeof(uint32_t)), 1));
-    if (per > KSG_HEADROOM_CHUNK) per -= per % KSG_HEADROOM_CHUNK;
-    per = std::min(per, n);
-    if ((rc = c->d_hcounts.grow(c, (size_t)per * c->N))) return rc;
-  }
-  if (!c->ev_x0) {
-    HIPCHK(c, hipEventCreate(&c->ev_x0));
-    HIPCHK(c, hipEventCreate(&c->ev_x1));
-  }
-  for (uint32_t a = 0; a < n; a += per) {
-    const uint32_t m = std::min(per, n - a);
-    HIPCHK(c, hipEventRecord(c->ev_x0, c->st));
+  const uint32_t per = query_per(c->headroom_stage, counts ? (size_t)c->N * sizeof(uint32_t) : 0, KSG_HEADROOM_CHUNK, n);
+  if (counts && (rc = c->d_hcounts.grow(c, (size_t)per * c->N))) return rc;
+  const auto launch = [&](uint32_t a, uint32_t m) {
     HIPCHK(c, ksg_launch_headroom(c->dev, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m, limit, c->headroom_div,
                                   counts ? c->d_hcounts.p : nullptr, reinterpret_cast<uint64_t*>(ho) + a,
                                   reinterpret_cast<uint32_t*>(ho + o_max) + a, reinterpret_cast<uint32_t*>(ho + o_fit) + a,
                                   reinterpret_cast<uint32_t*>(ho + o_hist) + (size_t)a * KSG_HEADROOM_SLOTS,
                                   ho + o_err + a, c->st));
-    HIPCHK(c, hipEventRecord(c->ev_x1, c->st));
+    return KSG_OK;
+  };
+  const auto copies = [&](uint32_t a, uint32_t m, bool last) {
     if (counts)
       HIPCHK(c, hipMemcpyAsync(counts + (size_t)a * c->N, c->d_hcounts, (size_t)m * c->N * sizeof(uint32_t),
                                hipMemcpyDeviceToHost, c->st));
-    if (a + per >= n)  // the last chunk's wait also brings the per-pod results back
-      HIPCHK(c, hipMemcpyAsync(c->h_dn, ho, ob, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));  // (the staging buffer is reused by the next chunk)
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_x0, c->ev_x1));
-    c->last_headroom_ms += ms;
-  }
+    if (last) HIPCHK(c, hipMemcpyAsync(c->h_dn, ho, ob, hipMemcpyDeviceToHost, c->st));
+    return KSG_OK;
+  };
+  rc = query_chunks(c, n, per, &c->last_headroom_ms, std::cref(launch), std::cref(copies));
+  if (rc) return rc;
   memcpy(total, c->h_dn, (size_t)n * 8);
   memcpy(max_count, c->h_dn + o_max, (size_t)n * 4);
   memcpy(fit_count, c->h_dn + o_fit, (size_t)n * 4);

@@ -8,8 +8,8 @@
 //                 index among them (a pair with a holder outside the list keeps its bit);
 //   peers         per explained pod its ServiceAffinity peer as of its position,
 //
-// uploaded in one copy. The protocol, the validation and the chunking are ksg_explain_batch's
-// (ksg_runtime.cpp); the context and the helpers shared with it are in ksg_host.h.
+// uploaded in one copy. The protocol, the validation, the uploads and the chunk loop are the
+// read-only batch queries' frame (query_enter ... query_chunks, ksg_host.h).
 #include <cstring>
 
 #include "ksg_host.h"
@@ -49,25 +49,16 @@ int ksg_explain_without(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext,
                         uint8_t* codes, uint32_t* hist, uint8_t* err) {
   if (!c || (n && (!pods || !hist || !err))) return KSG_ERR_ARG;
   KSG_LOCK(c);
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
-  if (ext && !c->ext_on) return fail(c, KSG_ERR_STATE, "extensions are off");
-  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
-  if (int rc0 = flush_deferred(c)) return rc0;  // (the mirror now holds the last batch)
-  if (int rs = cluster_ok(c)) return rs;
-  HIPCHK(c, hipSetDevice(c->device));
-  c->last_without_ms = 0.0;
-  if (n == 0) return KSG_OK;
-  if (c->N == 0) return KSG_NONODES;
-  if (n_ids && !ids) return fail(c, KSG_ERR_ARG, "ids missing");
-  if (n_absent && (!absent_uids || !first_absent)) return fail(c, KSG_ERR_ARG, "absent list or positions missing");
   int rc;
-  for (uint32_t i = 0; i < n; ++i) {
-    if ((rc = check_pod(c, pods + i, ids, n_ids))) return rc;
-    if (ext && ((rc = check_ext_range(c, ext + i, n_ids)) || (rc = check_taint_ids(c, ext + i, ids)))) return rc;
+  if ((rc = query_enter(c, ext, n, ids, n_ids, &c->last_without_ms))) return rc == kQueryDone ? KSG_OK : rc;
+  if (n_absent && (!absent_uids || !first_absent)) return fail(c, KSG_ERR_ARG, "absent list or positions missing");
+  const auto position = [&](uint32_t i) {
     if (first_absent && first_absent[i] > n_absent)
       return fail(c, KSG_ERR_ARG, "first_absent[%u] = %u > n_absent %u", i, first_absent[i], n_absent);
-  }
-  // the list: committed uids, each once
+    return KSG_OK;
+  };
+  if ((rc = query_validate(c, pods, ext, n, ids, n_ids, std::cref(position)))) return rc;
+  // the list: committed uids, each once (an invalid one leaves the device untouched)
   const uint32_t N = c->N, ns = c->ext_on ? c->ext.n_scalar : 0;
   std::vector<Listed> on;
   std::unordered_map<uint64_t, uint32_t> idx_of_seq;  // a listed pod's commit sequence number -> list index
@@ -164,14 +155,8 @@ int ksg_explain_without(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext,
     }
     peer[i] = pc.at(fa[i]);
   }
-  if ((rc = flush_patches(c))) return rc;
-  if ((rc = upload_pods(c, pods, n, ids, n_ids))) return rc;
-  const ksg_pod_ext* dext = nullptr;
-  if (ext) {  // (no record: the extension filters are skipped, as an all-zero record passes them)
-    if ((rc = c->d_pext.grow(c, n))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_pext, ext, (size_t)n * sizeof(ksg_pod_ext), hipMemcpyHostToDevice, c->st));
-    dext = c->d_pext;
-  }
+  const ksg_pod_ext* dext;
+  if ((rc = query_upload(c, pods, ext, n, ids, n_ids, false, &dext))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->d_wtab, h, tb, hipMemcpyHostToDevice, c->st));
   uint8_t* const t = c->d_wtab;
   KsgWithout w{};
@@ -185,44 +170,32 @@ int ksg_explain_without(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext,
   w.nd_n = (uint32_t)E;
   w.n_absent = n_absent;
   // hist and err for the whole call; the per-node codes in a bounded staging buffer, a chunk
-  // of pods at a time (whole pod chunks of the kernel, at least one pod)
+  // of pods at a time
   const size_t hb = (size_t)n * KSG_EXPLAIN_SLOTS * sizeof(uint32_t);
   if ((rc = c->d_whist.grow(c, hb + n))) return rc;
   uint32_t* d_hist = reinterpret_cast<uint32_t*>(c->d_whist.p);
   uint8_t* d_err = c->d_whist + hb;
   HIPCHK(c, hipMemsetAsync(c->d_whist, 0, hb + n, c->st));
-  uint32_t per = 1u << 20;  // pods per launch (the grid's y extent stays far below 65,535)
-  if (codes) {
-    per = (uint32_t)std::min<size_t>(per, std::max<size_t>(c->without_stage / N, 1));
-    if (per > KSG_EXPLAIN_CHUNK) per -= per % KSG_EXPLAIN_CHUNK;
-    per = std::min(per, n);
-    if ((rc = c->d_wcodes.grow(c, (size_t)per * N))) return rc;
-  }
-  if (!c->ev_x0) {
-    HIPCHK(c, hipEventCreate(&c->ev_x0));
-    HIPCHK(c, hipEventCreate(&c->ev_x1));
-  }
-  for (uint32_t a = 0; a < n; a += per) {
-    const uint32_t m = std::min(per, n - a);
+  const uint32_t per = query_per(c->without_stage, codes ? N : 0, KSG_EXPLAIN_CHUNK, n);
+  if (codes && (rc = c->d_wcodes.grow(c, (size_t)per * N))) return rc;
+  const auto launch = [&](uint32_t a, uint32_t m) {
     w.first_absent = reinterpret_cast<const uint32_t*>(t + o_fa) + a;  // (offset like the pods)
     w.peer = aff ? reinterpret_cast<const int32_t*>(t + o_peer) + a : nullptr;
-    HIPCHK(c, hipEventRecord(c->ev_x0, c->st));
     HIPCHK(c, ksg_launch_explain_without(c->dev, w, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m,
                                          codes ? c->d_wcodes.p : nullptr, d_hist + (size_t)a * KSG_EXPLAIN_SLOTS,
                                          d_err + a, c->st));
-    HIPCHK(c, hipEventRecord(c->ev_x1, c->st));
+    return KSG_OK;
+  };
+  const auto copies = [&](uint32_t a, uint32_t m, bool last) {
     if (codes)
       HIPCHK(c, hipMemcpyAsync(codes + (size_t)a * N, c->d_wcodes, (size_t)m * N, hipMemcpyDeviceToHost, c->st));
-    if (a + per >= n) {  // the last chunk's wait also brings hist and err back
+    if (last) {  // straight into the caller's arrays
       HIPCHK(c, hipMemcpyAsync(hist, d_hist, hb, hipMemcpyDeviceToHost, c->st));
       HIPCHK(c, hipMemcpyAsync(err, d_err, n, hipMemcpyDeviceToHost, c->st));
     }
-    HIPCHK(c, hipStreamSynchronize(c->st));  // (the staging buffer is reused by the next chunk)
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_x0, c->ev_x1));
-    c->last_without_ms += ms;
-  }
-  return KSG_OK;
+    return KSG_OK;
+  };
+  return query_chunks(c, n, per, &c->last_without_ms, std::cref(launch), std::cref(copies));
 }
 
 int ksg_last_explain_without_ms(ksg_ctx* c, double* ms) {
