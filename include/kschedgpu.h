@@ -638,6 +638,83 @@ int ksg_explain_without(ksg_ctx* ctx, const ksg_pod* pods, const ksg_pod_ext* ex
  * the context's stream (the table upload and the copies out are not in it). Diagnostics. */
 int ksg_last_explain_without_ms(ksg_ctx* ctx, double* ms);
 
+/* ---- Preemption: victims per node and the node to preempt on ----
+ * The second half of preemption, after ksg_explain_without's "on which nodes would this pod
+ * fit if every lower-priority pod were evicted": which of those pods really have to leave,
+ * per node, and on which node the eviction hurts least. The model is the later
+ * kube-scheduler's selectVictimsOnNode plus pickOneNodeForPreemption (v1.10, without
+ * PodDisruptionBudgets); parity is unpinned, and the definition below, in terms of
+ * ksg_evaluate, is the specification. The inputs are ksg_explain_without's: n pending pods,
+ * an ordered list absent_uids of n_absent committed pods that the caller sorted by descending
+ * priority, and per pod i the position first_absent[i] of the first entry below its own
+ * priority. The library knows no priorities; the order carries them.
+ * For pod i and node x:
+ *   - Candidates. C(i,x) is the listed pods at positions >= first_absent[i] whose host is
+ *     node x, in list order. Listed pods on hosts outside the node list play no part.
+ *   - Base state. S0 is the current state with every pod of C(i,x) removed from node x. If
+ *     pod i's fail code on node x in S0 (what ksg_evaluate would report) is not 0, node x is
+ *     not a candidate for pod i.
+ *   - Reprieve. Otherwise C(i,x) is walked in list order, most important first, with R = {}:
+ *     pod c is reprieved (R += c) iff pod i's fail code on node x is still 0 with R + {c} put
+ *     back on the node; else c is a victim. V(i,x) = C(i,x) \ R, in list order.
+ *   - Only NoDiskConflict, PodFitsPorts, PodFitsResources and the extended resources change
+ *     when a pod is put back, exactly as ksg_evaluate tests them: wrapping totals, a capacity
+ *     of 0 fits everything, a pod that requests neither cpu nor memory skips
+ *     PodFitsResources, an extended resource counts only where the pod requests it. A
+ *     candidate that holds a host port or GCE PD the pod lists is therefore always a victim,
+ *     and a holder outside C(i,x) makes the node fail in S0. HostName, LabelsPresence and the
+ *     other static terms, MatchNodeSelector and the taints do not depend on the pods on the
+ *     node; a negative request of a candidate makes the greedy order matter.
+ * The node for pod i is the best candidate in this order (ties the project's way, rank
+ * descending):
+ *   1. the largest top(i,x), the smallest list index in V(i,x), or n_absent when V is empty:
+ *      the most important victim is as unimportant as possible, and a node that needs no
+ *      eviction beats every node that does;
+ *   2. the fewest victims;
+ *   3. the highest node rank.
+ * v1.10's "smallest sum of victim priorities" criterion needs magnitudes the ordering does
+ * not carry and is left out, as are PodDisruptionBudgets.
+ * ServiceAffinity: the predicate's peer depends on pods on other nodes, and evicting the
+ * peer itself is not a per-node question. A context whose configuration has a
+ * ServiceAffinity predicate gets KSG_ERR_STATE (ksg_last_error says why), nothing written;
+ * ksg_explain_without stays the tool there.
+ * Outputs per pod i: best_node[i] (-1: no candidate), n_victims[i] = |V| on it (the true
+ * count even past max_victims), victims[i][..] the first max_victims list indices of V in
+ * list order, padded with 0xffffffff, cand_count[i] the candidate nodes and free_count[i]
+ * those with an empty V; optionally node_victims[i][x] = |V(i,x)|, KSG_PREEMPT_NOFIT where
+ * node x is not a candidate. Invariants: cand_count[i] is ksg_explain_without's hist[i][0]
+ * for the same inputs and free_count[i] is ksg_explain_batch's hist[i][0]; with
+ * n_absent == 0 or first_absent[i] == n_absent, best_node[i] is the highest-rank fitting
+ * node and n_victims[i] is 0.
+ * Nothing is removed. The call changes nothing a later call can observe: not the committed
+ * totals, the generator state, the uid bookkeeping, the extended-resource usage or the
+ * results and the path of any later batch.
+ * Protocol and validation are ksg_explain_without's: ext, uid is ignored, n == 0 (KSG_OK,
+ * nothing written), KSG_ERR_STATE while a ksg_schedule_begin is pending or for ext without
+ * extensions, KSG_NONODES for an empty node list, every node covered on every rank of a
+ * sharded context with no exchange. KSG_ERR_ARG, with nothing written: an absent_uids entry
+ * that is not a committed uid, the same uid twice, first_absent[i] > n_absent, absent_uids
+ * or first_absent NULL with n_absent > 0, best_node, n_victims, cand_count or free_count
+ * NULL with n > 0, victims NULL with max_victims > 0, max_victims > KSG_PREEMPT_MAX_VICTIMS.
+ * The pods are processed in chunks whose per-node counts and per-tile partial results fit
+ * a device staging budget (64 MiB; the environment variable KSG_PREEMPT_STAGE_BYTES, read by
+ * ksg_create, overrides it). */
+#define KSG_PREEMPT_MAX_VICTIMS 256
+#define KSG_PREEMPT_NOFIT 0xffffffffu
+int ksg_preempt_batch(ksg_ctx* ctx, const ksg_pod* pods, const ksg_pod_ext* ext /* NULL: all-zero */,
+                      uint32_t n, const uint32_t* ids, uint32_t n_ids,
+                      const uint64_t* absent_uids /* n_absent; may be NULL iff n_absent == 0 */,
+                      uint32_t n_absent, const uint32_t* first_absent /* n; may be NULL iff n_absent == 0 */,
+                      uint32_t max_victims /* 0..KSG_PREEMPT_MAX_VICTIMS */,
+                      int32_t* best_node /* n; -1: no candidate */,
+                      uint32_t* n_victims /* n */,
+                      uint32_t* victims /* n * max_victims; NULL iff max_victims == 0 */,
+                      uint32_t* cand_count /* n */, uint32_t* free_count /* n */,
+                      uint32_t* node_victims /* optional, n * n_nodes */);
+/* Device time (ms) of the last ksg_preempt_batch's kernel launches, from HIP events on the
+ * context's stream (the table upload and the copies out are not in it). Diagnostics. */
+int ksg_last_preempt_ms(ksg_ctx* ctx, double* ms);
+
 /* ---- Ranked hosts for many pods (prioritizeNodes + the sorted HostPriorityList) ----
  * One device pass filters and scores n pods against every node, as ksg_evaluate does
  * for one (generic_scheduler.go:84-96, 136-177), and returns per pod i, against the

@@ -64,6 +64,8 @@ ROOM_MEMORY = 5
 ROOM_SCALAR0 = 6  # + r, r < MAX_SCALAR
 HEADROOM_ERR_PEER = 1
 HEADROOM_ERR_NEGATIVE = 2
+PREEMPT_MAX_VICTIMS = 256  # ksg_preempt_batch: the longest victim list written per pod
+PREEMPT_NOFIT = 0xFFFFFFFF  # ... node_victims where the node is not a candidate
 
 MAX_ANTI = 64
 MAX_LABEL_PREF = 32
@@ -239,6 +241,8 @@ EXPORTS = [
     "ksg_last_headroom_ms",
     "ksg_explain_without",
     "ksg_last_explain_without_ms",
+    "ksg_preempt_batch",
+    "ksg_last_preempt_ms",
 ]
 
 # int (*ksg_allgather_fn)(void* user, const void* send, void* recv, uint64_t bytes)
@@ -324,6 +328,8 @@ def load_library() -> C.CDLL:
         # (ctx, pods, ext | NULL, n, ids, n_ids, absent_uids | NULL, n_absent, first_absent | NULL, codes | NULL, hist, err)
         "ksg_explain_without": (C.c_int, [vp, vp, vp, U32, vp, U32, vp, U32, vp, vp, vp, vp]),
         "ksg_last_explain_without_ms": (C.c_int, [vp, P(C.c_double)]),
+        "ksg_preempt_batch": (C.c_int, [vp, vp, vp, U32, vp, U32, vp, U32, vp, U32, vp, vp, vp, vp, vp, vp]),
+        "ksg_last_preempt_ms": (C.c_int, [vp, P(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

@@ -350,6 +350,46 @@ struct KsgNoneAbsent {
   __device__ __forceinline__ int64_t used(uint32_t, int64_t v) const { return v; }
 };
 
+// first position in [lo, hi) of the ascending array a whose value is >= v (hi: none)
+__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* __restrict__ a, uint32_t lo, uint32_t hi, uint32_t v) {
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// node_fail_l's view of touched node n at position fa of a KsgWithout list (ksg_explain_without.hip,
+// ksg_preempt.hip): the bounds [c0, c1) of its conflict row are loaded up front (in flight with
+// the walk's first bitmap loads); no search runs before the walk asks, so a lane that fails an
+// earlier predicate pays for none.
+struct KsgAbsentAt {
+  const KsgWithout& w;
+  const uint32_t n, fa, c0, c1;
+  mutable uint32_t e = 0, e1 = 0;  // the node's listed pods at or past the position: entries e.. of
+  mutable bool have_e = false;     // its row (e == e1: none), found at the first read of a total
+  __device__ __forceinline__ bool key_cleared(uint32_t key) const {
+    const uint32_t f = lower_bound_u32(w.cf_key, c0, c1, key);
+    return f < c1 && w.cf_key[f] == key && fa <= w.cf_min[f];
+  }
+  __device__ __forceinline__ void seek() const {
+    if (!have_e) {
+      e1 = w.nd_off[n + 1];
+      e = lower_bound_u32(w.nd_idx, w.nd_off[n], e1, fa);
+      have_e = true;
+    }
+  }
+  // remove_pod_impl's wrapping subtraction, all of the suffix at once. The search depends on
+  // the node and the position only, so its result serves every k: it is cached in the object,
+  // which is one lane's for one walk (node_fail_l reads cpu and memory together, so the
+  // search runs once there and the extended resources reuse it).
+  __device__ __forceinline__ int64_t used(uint32_t k, int64_t v) const {
+    seek();
+    return e < e1 ? (int64_t)((uint64_t)v - w.nd_sum[(size_t)k * w.nd_n + e]) : v;
+  }
+};
+
 // Filter: first failing predicate (fixed order) or 0. wi/bit locate node n in
 // the bitmaps; wi is wave-uniform for the scan kernels. `L` yields the pod's
 // list entries: L.port(i), L.pd(i), L.sel(i). `absent` is what the query takes away from

@@ -19,7 +19,7 @@
 // Nothing of the pass is restated here. The kernel is ksg_explain_pass (ksg_device.h) and the
 // predicates are node_fail_l's; this file only supplies what is taken away, as the two views
 // those templates ask for: KsgAbsent for the pass (the touched bit, the peer, the choice of
-// the walk) and KsgAbsentAt for node_fail_l (a touched node at a position: cleared conflict
+// the walk) and KsgAbsentAt (ksg_device.h) for node_fail_l (a touched node at a position: cleared conflict
 // bits and corrected totals, so a cleared disk bit lets the port, resource and later checks
 // report). A lane whose node is not touched, and every lane of a pod with first_absent ==
 // n_absent, runs node_fail<false> as it is. The lookups are binary searches on the lane's own
@@ -28,42 +28,6 @@
 
 #include "ksg_device.h"
 #include "ksg_launch.h"
-
-// first position in [lo, hi) of the ascending array a whose value is >= v (hi: none)
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* __restrict__ a, uint32_t lo, uint32_t hi, uint32_t v) {
-  while (lo < hi) {
-    const uint32_t mid = lo + ((hi - lo) >> 1);
-    if (a[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// node_fail_l's view of touched node n at position fa: the bounds [c0, c1) of its conflict row
-// are loaded up front (in flight with the walk's first bitmap loads); no search runs before the
-// walk asks, so a lane that fails an earlier predicate pays for none.
-struct KsgAbsentAt {
-  const KsgWithout& w;
-  const uint32_t n, fa, c0, c1;
-  mutable uint32_t e = 0, e1 = 0;  // the node's listed pods at or past the position: entries e.. of
-  mutable bool have_e = false;     // its row (e == e1: none), found at the first read of a total
-  __device__ __forceinline__ bool key_cleared(uint32_t key) const {
-    const uint32_t f = lower_bound_u32(w.cf_key, c0, c1, key);
-    return f < c1 && w.cf_key[f] == key && fa <= w.cf_min[f];
-  }
-  // remove_pod_impl's wrapping subtraction, all of the suffix at once. The search depends on
-  // the node and the position only, so its result serves every k: it is cached in the object,
-  // which is one lane's for one walk (node_fail_l reads cpu and memory together, so the
-  // search runs once there and the extended resources reuse it).
-  __device__ __forceinline__ int64_t used(uint32_t k, int64_t v) const {
-    if (!have_e) {
-      e1 = w.nd_off[n + 1];
-      e = lower_bound_u32(w.nd_idx, w.nd_off[n], e1, fa);
-      have_e = true;
-    }
-    return e < e1 ? (int64_t)((uint64_t)v - w.nd_sum[(size_t)k * w.nd_n + e]) : v;
-  }
-};
 
 // ksg_explain_pass's view: the peer as of the pod's position instead of d.svc_peer (the
 // spreading terms, which no predicate reads, stay 0), and the hooked walk for a touched lane

@@ -1,6 +1,6 @@
 // ksg_host.h — what the host translation units share: the context (struct ksg_ctx), the
 // owning scratch-buffer types, the error macros, the environment switches' parsers and the
-// helpers ksg_runtime.cpp defines and ksg_batch.cpp and ksg_without.cpp call, among them the
+// helpers ksg_runtime.cpp defines and ksg_batch.cpp, ksg_without.cpp and ksg_preempt.cpp call, among them the
 // frame of the read-only batch queries (query_enter ... query_chunks).
 #ifndef KSG_HOST_H_
 #define KSG_HOST_H_
@@ -222,6 +222,15 @@ struct ksg_ctx {
   HostBuf h_wtab;
   size_t without_stage = (size_t)64 << 20;
   double last_without_ms = 0.0;
+  // ksg_preempt_batch (ksg_preempt.cpp): per chunk of pods the tile partials (KsgPreemptPart) and,
+  // where asked for, the per-node victim counts (together bounded: preempt_stage bytes,
+  // KSG_PREEMPT_STAGE_BYTES), and for the whole call int32 best[n], uint32 victims[n], cand[n],
+  // free[n], then the victim lists uint32[n][max_victims] (one buffer, one copy out). Its tables
+  // share d_wtab / h_wtab with ksg_explain_without.
+  DevBuf<uint8_t> d_vpart, d_vout;
+  DevBuf<uint32_t> d_vnode;
+  size_t preempt_stage = (size_t)64 << 20;
+  double last_preempt_ms = 0.0;
   std::vector<KsgPatch> patches;
 
   // host mirror
@@ -397,8 +406,8 @@ bool anti_on(const ksg_ctx* c);
 uint8_t* rec_buf(ksg_ctx* c);
 
 // ---- the read-only batch queries' frame -------------------------------------------
-// ksg_explain_batch, ksg_prioritize_batch, ksg_headroom_batch (ksg_runtime.cpp) and
-// ksg_explain_without (ksg_without.cpp) answer for n pods against the device state as it
+// ksg_explain_batch, ksg_prioritize_batch, ksg_headroom_batch (ksg_runtime.cpp),
+// ksg_explain_without (ksg_without.cpp) and ksg_preempt_batch (ksg_preempt.cpp) answer for n pods against the device state as it
 // stands, in one or more launches over chunks of pods. Each is: its null-pointer check, the
 // lock, its own argument checks, then these steps in this order, with what only it does
 // (buffers, zeroing, tables, where the results land) in between. Every step returns a KSG_*
@@ -430,6 +439,22 @@ uint32_t query_per(size_t budget, size_t bytes_per_pod, uint32_t chunk, uint32_t
 // std::cref: a std::function holding a reference allocates nothing.)
 int query_chunks(ksg_ctx* c, uint32_t n, uint32_t per, double* last_ms, const std::function<int(uint32_t, uint32_t)>& launch,
                  const std::function<int(uint32_t, uint32_t, bool)>& copies);
+// ---- ksg_without.cpp's table builder, shared with ksg_preempt.cpp -------------------------
+// The tables of an ordered list of committed pods (KsgWithout, ksg_internal.h), built in
+// c->h_wtab with their device addresses in c->d_wtab (both grown here): the caller copies
+// `bytes` across on the stream after its uploads. w.first_absent and w.peer point at pod 0's
+// entries (a chunk offsets them). peers: look up each pod's ServiceAffinity peer as of its
+// position (w.peer stays nullptr without the predicate); entry_keys: also the conflict keys of
+// every row entry (ek). KSG_ERR_ARG, nothing built, for an unknown uid or a uid listed twice.
+struct WithoutTables {
+  KsgWithout w{};
+  KsgPreemptKeys ek{};
+  size_t bytes = 0;
+};
+int without_tables(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint64_t* absent_uids, uint32_t n_absent,
+                   const uint32_t* first_absent, bool peers, bool entry_keys, WithoutTables* tabs);
+// query_validate's per-pod extra of both callers: first_absent[i] <= n_absent
+int without_position(ksg_ctx* c, const uint32_t* first_absent, uint32_t i, uint32_t n_absent);
 extern "C" {  // (defined among the entry points, inside ksg_runtime.cpp's extern "C" block)
 int remove_pod_impl(ksg_ctx* c, uint64_t uid);
 int note_ext(ksg_ctx* c, const ksg_pod* p, const ksg_pod_ext* e, size_t n_ids);

@@ -280,6 +280,22 @@ struct KsgWithout {
   uint32_t nd_n, n_absent;
 };
 
+// ksg_preempt_batch (ksg_preempt.hip) keeps that tiling and reads KsgWithout's tables (without
+// the peers) plus one more: the conflict keys of each entry of the node rows. Per (pod, node
+// tile) the first pass leaves one KsgPreemptPart; the second reads them, one wave per pod.
+struct KsgPreemptKeys {
+  const uint32_t* ek_off;  // [nd_n + 1] CSR by row entry (nd_idx's positions) of the listed pod's conflict keys ...
+  const uint32_t* ek_key;  // ... ports and GCE PDs, in the record's order
+};
+struct KsgPreemptPart {
+  uint64_t key;    // best candidate of the tile: (top << 32) | ~victims, larger is better
+  uint32_t node1;  // ... its node rank + 1 (0: the tile has no candidate)
+  uint32_t cand;   // candidate nodes
+  uint32_t free_;  // candidates without a victim
+  uint32_t pad;
+};
+static_assert(sizeof(KsgPreemptPart) == 24, "KsgPreemptPart layout");
+
 // ksg_headroom_kernel (ksg_headroom.hip) keeps that tiling
 #define KSG_HEADROOM_TILE KSG_EXPLAIN_TILE
 #define KSG_HEADROOM_CHUNK KSG_EXPLAIN_CHUNK

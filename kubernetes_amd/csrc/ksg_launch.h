@@ -69,6 +69,14 @@ hipError_t ksg_launch_explain_without(const KsgDev& d, const KsgWithout& w, cons
                                       const uint32_t* ids, uint32_t n_pods, uint8_t* codes, uint32_t* hist, uint8_t* err,
                                       hipStream_t st);
 
+// ksg_preempt.hip (every per-pod array, w.first_absent included, is indexed from `pods`; part =
+// KsgPreemptPart[n_pods][ksg_preempt_tiles(d)]; w.peer is not read)
+uint32_t ksg_preempt_tiles(const KsgDev& d);
+hipError_t ksg_launch_preempt(const KsgDev& d, const KsgWithout& w, const KsgPreemptKeys& ek, const ksg_pod* pods,
+                              const ksg_pod_ext* exts, const uint32_t* ids, uint32_t n_pods, uint32_t max_victims,
+                              uint32_t* node_victims, KsgPreemptPart* part, int32_t* best_node, uint32_t* n_victims,
+                              uint32_t* victims, uint32_t* cand_count, uint32_t* free_count, hipStream_t st);
+
 // ksg_headroom.hip (the per-pod arrays are indexed from `pods`; div: udiv_capped's variant)
 hipError_t ksg_launch_headroom(const KsgDev& d, const ksg_pod* pods, const ksg_pod_ext* exts, const uint32_t* ids,
                                uint32_t n_pods, uint32_t limit, int div, uint32_t* counts, uint64_t* total,

@@ -961,6 +961,8 @@ static int create_impl(const ksg_config* cfg, int device, int rank, int world, c
   c->headroom_div = (int)env_int("KSG_HEADROOM_DIV", c->headroom_div, 0, 2);
   // ksg_explain_without: the staging budget of the per-node codes (the same test knob)
   c->without_stage = (size_t)env_int("KSG_EXPLAIN_WITHOUT_STAGE_BYTES", (int64_t)c->without_stage, 1, (int64_t)1 << 40);
+  // ksg_preempt_batch: the staging budget of the tile partials and per-node counts (the same test knob)
+  c->preempt_stage = (size_t)env_int("KSG_PREEMPT_STAGE_BYTES", (int64_t)c->preempt_stage, 1, (int64_t)1 << 40);
   // The exchange path (shard scan, all-gather of per-shard records, replicated
   // resolve) runs for world > 1, and for a 1-rank RCCL communicator when the caller
   // passes an nccl_id with world == 1 (RCCL itself exercised on a single GPU).

@@ -9,7 +9,9 @@
 //   peers         per explained pod its ServiceAffinity peer as of its position,
 //
 // uploaded in one copy. The protocol, the validation, the uploads and the chunk loop are the
-// read-only batch queries' frame (query_enter ... query_chunks, ksg_host.h).
+// read-only batch queries' frame (query_enter ... query_chunks, ksg_host.h). The tables are
+// built by without_tables, which ksg_preempt_batch (ksg_preempt.cpp) calls too, with a fourth
+// table (the conflict keys of every row entry) in place of the peers.
 #include <cstring>
 
 #include "ksg_host.h"
@@ -42,22 +44,17 @@ inline size_t align8(size_t x) { return (x + 7) & ~(size_t)7; }
 
 }  // namespace
 
-extern "C" {
+#pragma GCC visibility push(hidden)
 
-int ksg_explain_without(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
-                        uint32_t n_ids, const uint64_t* absent_uids, uint32_t n_absent, const uint32_t* first_absent,
-                        uint8_t* codes, uint32_t* hist, uint8_t* err) {
-  if (!c || (n && (!pods || !hist || !err))) return KSG_ERR_ARG;
-  KSG_LOCK(c);
+int without_position(ksg_ctx* c, const uint32_t* first_absent, uint32_t i, uint32_t n_absent) {
+  if (first_absent && first_absent[i] > n_absent)
+    return fail(c, KSG_ERR_ARG, "first_absent[%u] = %u > n_absent %u", i, first_absent[i], n_absent);
+  return KSG_OK;
+}
+
+int without_tables(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint64_t* absent_uids, uint32_t n_absent,
+                   const uint32_t* first_absent, bool peers, bool entry_keys, WithoutTables* tabs) {
   int rc;
-  if ((rc = query_enter(c, ext, n, ids, n_ids, &c->last_without_ms))) return rc == kQueryDone ? KSG_OK : rc;
-  if (n_absent && (!absent_uids || !first_absent)) return fail(c, KSG_ERR_ARG, "absent list or positions missing");
-  const auto position = [&](uint32_t i) {
-    if (first_absent && first_absent[i] > n_absent)
-      return fail(c, KSG_ERR_ARG, "first_absent[%u] = %u > n_absent %u", i, first_absent[i], n_absent);
-    return KSG_OK;
-  };
-  if ((rc = query_validate(c, pods, ext, n, ids, n_ids, std::cref(position)))) return rc;
   // the list: committed uids, each once (an invalid one leaves the device untouched)
   const uint32_t N = c->N, ns = c->ext_on ? c->ext.n_scalar : 0;
   std::vector<Listed> on;
@@ -76,12 +73,15 @@ int ksg_explain_without(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext,
             [](const Listed& a, const Listed& b) { return a.node != b.node ? a.node < b.node : a.idx < b.idx; });
   // conflict keys only listed pods hold: the listed occurrences equal the mirror's count
   std::unordered_map<uint64_t, Conflict> held;
-  for (const Listed& l : on)
+  size_t K = 0;  // the row entries' keys, all told
+  for (const Listed& l : on) {
+    K += l.r->keys.size();
     for (uint32_t k : l.r->keys) {
       auto ins = held.emplace(((uint64_t)k << 32) | l.node, Conflict{l.node, k, l.idx, 0});
       ins.first->second.min_idx = std::min(ins.first->second.min_idx, l.idx);
       ++ins.first->second.held;
     }
+  }
   std::vector<Conflict> cf;
   for (const auto& kv : held) {
     const auto kit = c->key_ref.find(kv.first);
@@ -89,14 +89,16 @@ int ksg_explain_without(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext,
   }
   std::sort(cf.begin(), cf.end(),
             [](const Conflict& a, const Conflict& b) { return a.node != b.node ? a.node < b.node : a.key < b.key; });
-  const bool aff = (c->dev.preds & KSG_PRED_SERVICEAFFINITY) != 0;  // (else no peer is looked up)
+  const bool aff = peers && (c->dev.preds & KSG_PRED_SERVICEAFFINITY) != 0;  // (else no peer is looked up)
   // one buffer: nd_sum uint64[2 + ns][E], touched uint64[nw], then the uint32 arrays nd_off[N + 1],
-  // nd_idx[E], cf_off[N + 1], cf_key[F], cf_min[F], first_absent[n], peer int32[n]
+  // nd_idx[E], cf_off[N + 1], cf_key[F], cf_min[F], first_absent[n], peer int32[n], and with
+  // entry_keys ek_off[E + 1], ek_key[K]
   const size_t E = on.size(), F = cf.size();
   const size_t o_touch = (2 + (size_t)ns) * E * 8, o_ndoff = o_touch + (size_t)c->nw * 8;
   const size_t o_ndidx = o_ndoff + ((size_t)N + 1) * 4, o_cfoff = o_ndidx + E * 4, o_cfkey = o_cfoff + ((size_t)N + 1) * 4;
   const size_t o_cfmin = o_cfkey + F * 4, o_fa = o_cfmin + F * 4, o_peer = o_fa + (size_t)n * 4;
-  const size_t tb = align8(o_peer + (size_t)n * 4);
+  const size_t o_ekoff = o_peer + (size_t)n * 4, o_ekkey = o_ekoff + (entry_keys ? (E + 1) * 4 : 0);
+  const size_t tb = align8(o_ekkey + (entry_keys ? K * 4 : 0));
   if ((rc = c->h_wtab.grow(c, tb)) || (rc = c->d_wtab.grow(c, tb))) return rc;
   uint8_t* const h = c->h_wtab;
   memset(h, 0, o_ndidx);  // (the sums are written below; touched and nd_off start from zero)
@@ -129,6 +131,16 @@ int ksg_explain_without(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext,
     ++cf_off[cf[f].node + 1];
   }
   for (uint32_t x = 0; x < N; ++x) cf_off[x + 1] += cf_off[x];
+  if (entry_keys) {  // each row entry's own conflict keys (PodRec::keys)
+    uint32_t* const ek_off = reinterpret_cast<uint32_t*>(h + o_ekoff);
+    uint32_t* const ek_key = reinterpret_cast<uint32_t*>(h + o_ekkey);
+    uint32_t k = 0;
+    for (size_t e = 0; e < E; ++e) {
+      ek_off[e] = k;
+      for (uint32_t key : on[e].r->keys) ek_key[k++] = key;
+    }
+    ek_off[E] = k;
+  }
   // the positions, and the peers as of each pod's position (one walk per service)
   std::unordered_map<int32_t, PeerChain> chains;
   for (uint32_t i = 0; i < n; ++i) {
@@ -155,11 +167,9 @@ int ksg_explain_without(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext,
     }
     peer[i] = pc.at(fa[i]);
   }
-  const ksg_pod_ext* dext;
-  if ((rc = query_upload(c, pods, ext, n, ids, n_ids, false, &dext))) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->d_wtab, h, tb, hipMemcpyHostToDevice, c->st));
   uint8_t* const t = c->d_wtab;
-  KsgWithout w{};
+  KsgWithout& w = tabs->w;
+  w = KsgWithout{};
   w.nd_sum = reinterpret_cast<const uint64_t*>(t);
   w.touched = reinterpret_cast<const uint64_t*>(t + o_touch);
   w.nd_off = reinterpret_cast<const uint32_t*>(t + o_ndoff);
@@ -167,8 +177,42 @@ int ksg_explain_without(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext,
   w.cf_off = reinterpret_cast<const uint32_t*>(t + o_cfoff);
   w.cf_key = reinterpret_cast<const uint32_t*>(t + o_cfkey);
   w.cf_min = reinterpret_cast<const uint32_t*>(t + o_cfmin);
+  w.first_absent = reinterpret_cast<const uint32_t*>(t + o_fa);
+  w.peer = aff ? reinterpret_cast<const int32_t*>(t + o_peer) : nullptr;
   w.nd_n = (uint32_t)E;
   w.n_absent = n_absent;
+  tabs->ek = KsgPreemptKeys{};
+  if (entry_keys) {
+    tabs->ek.ek_off = reinterpret_cast<const uint32_t*>(t + o_ekoff);
+    tabs->ek.ek_key = reinterpret_cast<const uint32_t*>(t + o_ekkey);
+  }
+  tabs->bytes = tb;
+  return KSG_OK;
+}
+
+#pragma GCC visibility pop
+
+extern "C" {
+
+int ksg_explain_without(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
+                        uint32_t n_ids, const uint64_t* absent_uids, uint32_t n_absent, const uint32_t* first_absent,
+                        uint8_t* codes, uint32_t* hist, uint8_t* err) {
+  if (!c || (n && (!pods || !hist || !err))) return KSG_ERR_ARG;
+  KSG_LOCK(c);
+  int rc;
+  if ((rc = query_enter(c, ext, n, ids, n_ids, &c->last_without_ms))) return rc == kQueryDone ? KSG_OK : rc;
+  if (n_absent && (!absent_uids || !first_absent)) return fail(c, KSG_ERR_ARG, "absent list or positions missing");
+  const auto position = [&](uint32_t i) { return without_position(c, first_absent, i, n_absent); };
+  if ((rc = query_validate(c, pods, ext, n, ids, n_ids, std::cref(position)))) return rc;
+  WithoutTables tabs;
+  if ((rc = without_tables(c, pods, n, absent_uids, n_absent, first_absent, true, false, &tabs))) return rc;
+  const uint32_t N = c->N;
+  const ksg_pod_ext* dext;
+  if ((rc = query_upload(c, pods, ext, n, ids, n_ids, false, &dext))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->d_wtab, c->h_wtab, tabs.bytes, hipMemcpyHostToDevice, c->st));
+  const uint32_t* const d_fa = tabs.w.first_absent;
+  const int32_t* const d_peer = tabs.w.peer;
+  KsgWithout w = tabs.w;
   // hist and err for the whole call; the per-node codes in a bounded staging buffer, a chunk
   // of pods at a time
   const size_t hb = (size_t)n * KSG_EXPLAIN_SLOTS * sizeof(uint32_t);
@@ -179,8 +223,8 @@ int ksg_explain_without(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext,
   const uint32_t per = query_per(c->without_stage, codes ? N : 0, KSG_EXPLAIN_CHUNK, n);
   if (codes && (rc = c->d_wcodes.grow(c, (size_t)per * N))) return rc;
   const auto launch = [&](uint32_t a, uint32_t m) {
-    w.first_absent = reinterpret_cast<const uint32_t*>(t + o_fa) + a;  // (offset like the pods)
-    w.peer = aff ? reinterpret_cast<const int32_t*>(t + o_peer) + a : nullptr;
+    w.first_absent = d_fa + a;  // (offset like the pods)
+    w.peer = d_peer ? d_peer + a : nullptr;
     HIPCHK(c, ksg_launch_explain_without(c->dev, w, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m,
                                          codes ? c->d_wcodes.p : nullptr, d_hist + (size_t)a * KSG_EXPLAIN_SLOTS,
                                          d_err + a, c->st));

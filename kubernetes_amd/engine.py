@@ -336,6 +336,48 @@ class DeviceScheduler:
         self._lib.ksg_last_explain_without_ms(self._ctx, C.byref(ms))
         return ms.value
 
+    def preempt(self, batch: PodBatch, absent_uids, first_absent, max_victims: int = 16, want_per_node: bool = False):
+        """ksg_preempt_batch: which committed pods would have to leave for each pod of `batch`,
+        per node, and the node to preempt on. `absent_uids` lists the removable committed pods by
+        descending priority and `first_absent[i]` is the first entry below pod i's priority, as
+        explain_without() takes them; nothing is removed. On a node the pod fits with all of its
+        removable pods away, they are put back one by one, most important first, while the pod
+        still fits; the rest are the node's victims. The chosen node has the least important
+        most-important victim (none at all first), then the fewest victims, then the highest rank.
+        -> (best_node int32[n] (-1: no candidate), n_victims uint32[n], victims uint32[n,
+        max_victims] (list indices in list order, 0xffffffff padding), cand_count uint32[n],
+        free_count uint32[n] (candidates that need no eviction), node_victims uint32[n, N] | None
+        (want_per_node; abi.PREEMPT_NOFIT where the node is no candidate)). A configuration with
+        a ServiceAffinity predicate raises KsgError (KSG_ERR_STATE)."""
+        n = len(batch)
+        pods = np.ascontiguousarray(batch.pods, dtype=abi.POD_DTYPE)
+        ids = _u32(batch.ids if len(batch.ids) else np.zeros(1, np.uint32))
+        ext = None if batch.ext is None else np.ascontiguousarray(batch.ext, dtype=abi.POD_EXT_DTYPE)
+        uids = np.ascontiguousarray(absent_uids, dtype=np.uint64)
+        fa = _u32(first_absent)
+        if len(fa) != n:
+            raise ValueError(f"first_absent has {len(fa)} entries for {n} pods")
+        best = np.full(n, -1, np.int32)
+        nv = np.zeros(n, np.uint32)
+        victims = np.full((n, max_victims), 0xFFFFFFFF, np.uint32)
+        cand = np.zeros(n, np.uint32)
+        free = np.zeros(n, np.uint32)
+        per_node = np.full((n, self.n_nodes), abi.PREEMPT_NOFIT, np.uint32) if want_per_node else None
+        rc = self._lib.ksg_preempt_batch(self._ctx, abi.ptr(pods), abi.ptr(ext), n, abi.ptr(ids), len(batch.ids),
+                                         abi.ptr(uids) if len(uids) else None, len(uids), abi.ptr(fa) if n else None,
+                                         int(max_victims), abi.ptr(best), abi.ptr(nv),
+                                         abi.ptr(victims) if max_victims else None, abi.ptr(cand), abi.ptr(free),
+                                         abi.ptr(per_node) if want_per_node and per_node.size else None)
+        if rc not in (abi.KSG_OK, abi.KSG_NONODES):
+            self._err(rc)
+        return best, nv, victims, cand, free, per_node
+
+    def last_preempt_ms(self) -> float:
+        """Device ms of the last preempt()'s kernel launches (HIP events)."""
+        ms = C.c_double(0)
+        self._lib.ksg_last_preempt_ms(self._ctx, C.byref(ms))
+        return ms.value
+
     def prioritize(self, batch: PodBatch, top: int = 0, want_scores: bool = False):
         """ksg_prioritize_batch: filter and score every pod of `batch` against every node of the
         cluster as it stands, in one device pass, committing nothing.

@@ -390,6 +390,71 @@ class GPUScheduler:
             out.append(rec)
         return out
 
+    # ---- dry run: preemption ------------------------------------------------------------
+    def _committed(self) -> list:
+        """(pod, uid) of every listed pod the device holds (after a _sync), in uid order."""
+        out = []
+        if self._events is not None:
+            m = self._events.modeler
+            stores = {PodMirror.SCHED: m.scheduled_pods.store, PodMirror.ASSUMED: m.assumed_pods.store}
+            for (src, key), uid in self._events.on_device.items():
+                p, ok = stores[src].get_by_key(key)
+                if ok:
+                    out.append((p, uid))
+        else:
+            by_id = {id(p): p for p in self.pod_lister.list(everything())}
+            out = [(by_id[pid], uid) for uid, _, pid in self._mirror.values() if pid in by_id]
+        out.sort(key=lambda t: t[1])
+        return out
+
+    def preempt(self, pods: Sequence[Pod], minion_lister, priority_of, max_victims: int = 16) -> list:
+        """Which pods would have to leave for each pending pod, from one ksg_preempt_batch:
+        the committed pods are sorted by priority_of(pod) descending (stable), and a pending pod
+        may evict those strictly below its own priority. Per pending pod: None when a node takes
+        it as things stand (schedule it, evict nothing); {"host": name, "victims": [namespace/name,
+        ...] (most important first, at most max_victims), "n_victims": their true number} for the
+        node where the eviction hurts least (the least important most-important victim, then the
+        fewest victims, then the highest host); a FitError against the state with every pod it
+        may evict taken away when even that leaves no node. Nothing is committed or removed.
+        NoMinionsError entries without nodes. Not available under a ServiceAffinity predicate
+        (KsgError)."""
+        nodes = minion_lister.list()
+        if len(nodes) == 0:
+            return [NoMinionsError() for _ in pods]
+        self._sync(nodes)
+        if not pods:
+            return []
+        listed = sorted(self._committed(), key=lambda t: -priority_of(t[0]))  # (stable)
+        prios = [priority_of(p) for p, _ in listed]
+        uids = [u for _, u in listed]
+        b = PodBatchBuilder(self.view, self.aff_labels)
+        for p in pods:
+            b.add(p, 0)  # (the call ignores uids)
+        batch = b.build()
+        pos = []
+        for p in pods:  # the first entry below the pod's own priority
+            mine = priority_of(p)
+            pos.append(sum(1 for q in prios if q >= mine))
+        best, nv, victims, cand, free, _ = self.engine.preempt(batch, uids, pos, max_victims=max_victims)
+        names = self.view.names
+        out: list = [None] * len(pods)
+        nofit = [i for i in range(len(pods)) if cand[i] == 0]
+        for i in range(len(pods)):
+            if free[i] > 0 or cand[i] == 0:
+                continue
+            out[i] = {"host": names[int(best[i])],
+                      "victims": [listed[int(j)][0].key() for j in victims[i] if j != 0xFFFFFFFF],
+                      "n_victims": int(nv[i])}
+        if nofit:
+            sub = PodBatch(batch.pods[nofit], batch.ids, None if batch.ext is None else batch.ext[nofit])
+            codes, hist, _ = self.engine.explain_without(sub, uids, [pos[i] for i in nofit])
+            for j, i in enumerate(nofit):
+                row = codes[j]
+                failed = {names[n]: {self.fail_names[int(row[n])]} for n in row.nonzero()[0]}
+                counts = {self.fail_names[c]: int(hist[j, c]) for c in range(1, hist.shape[1]) if hist[j, c]}
+                out[i] = FitError(pods[i], failed, counts)
+        return out
+
 
 def new_gpu_scheduler(config: SchedulerConfig, pod_lister, service_lister=None, random=None,
                       device: int = 0) -> GPUScheduler:
