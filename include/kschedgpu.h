@@ -204,7 +204,8 @@ int ksg_nccl_unique_id(void* out128);
 int ksg_destroy(ksg_ctx* ctx);
 const char* ksg_last_error(ksg_ctx* ctx);
 
-/* Replace the node set (MinionLister.List()). Resets all pod state.
+/* Replace the node set (MinionLister.List()). Resets all pod state
+ * (ksg_update_cluster, below, replaces it and keeps the pods).
  * pair_keys[p] = label-key id of label pair p, | KSG_PAIR_INVALID for a pair
  * SelectorFromSet would reject (pair 0 is reserved: "no node has it").
  * node_pairs holds each node's label pair ids. */
@@ -298,7 +299,9 @@ int ksg_schedule_batch_draws(ksg_ctx* ctx, const ksg_pod* pods, uint32_t n, cons
  * state) is stepped back over the draws of pods k+1..n-1. The caller then
  * re-batches pods k+1..n-1. pods / out_nodes are the last batch's arrays; every
  * rank of a sharded context makes the same call. KSG_ERR_ARG (nothing changed)
- * when k >= n, pod k found no node, or a placed pod's uid is not committed. */
+ * when k >= n, pod k found no node, or a placed pod's uid is not committed.
+ * The pods are removed by uid and out_nodes is read only for its sign, so the call
+ * also works after a ksg_update_cluster has renumbered the nodes. */
 int ksg_batch_unwind(ksg_ctx* ctx, const ksg_pod* pods, const int32_t* out_nodes, uint32_t n, uint32_t k,
                      uint64_t* rng_state, uint32_t* draws_kept);
 
@@ -553,6 +556,66 @@ int ksg_evaluate_ext(ksg_ctx* ctx, const ksg_pod* pod, const ksg_pod_ext* ext, c
  * used[r * n_nodes + n] = the requests of resource r of every pod on node n
  * (the extended-resource counterpart of ksg_read_requested). */
 int ksg_read_ext_used(ksg_ctx* ctx, int64_t* used);
+
+/* ---- A changed node list that keeps the pods ----
+ * ksg_set_cluster resets all pod state; ksg_update_cluster replaces the node list (a node
+ * joined, left, was cordoned, changed its labels or capacity) and keeps every live pod under
+ * its uid. The first seven arguments are ksg_set_cluster's, for the new list; n_services and
+ * the config stay as they are (a changed service list needs ksg_set_cluster).
+ *
+ * Hosts are renamed. old_to_new[r], for each of the old n_nodes ranks (NULL iff there were
+ * none), is the host id the pods of old node r now have: below the new n_nodes the node's new
+ * rank, at or above it a host outside the list (the node left; its pods count as
+ * ksg_add_pod(host_id >= n_nodes) counts them). (outside_old[j], outside_new[j]), j < n_outside,
+ * renames a host id that was outside the old list; a new id below n_nodes means that host joined
+ * the list and its pods now count on that node. Every outside host that holds a live pod must be
+ * listed (listed hosts without pods are harmless), and the whole renaming must be injective. New
+ * nodes nothing maps to start empty. ext: ksg_set_node_ext's arrays for the new list, NULL iff
+ * the context has no extensions.
+ *
+ * After KSG_OK every later call's result, and every word ksg_read_requested, ksg_read_state and
+ * ksg_read_ext_used return, is what a fresh context gives after ksg_set_cluster with the new
+ * arrays and the same n_services, ksg_set_node_ext with `ext`, and ksg_add_pod / ksg_add_pod_ext
+ * of every live pod in its original order of addition (commit order for scheduled pods) on its
+ * renamed host. So a service's peer is still its earliest-added live member (-2 when that host
+ * left the list), svc_max still counts hosts outside the list, and a conflict bit stays while
+ * any holder is on the node.
+ *
+ * Uids stay committed: ksg_remove_pod and the absent_uids lists of ksg_explain_without /
+ * ksg_preempt_batch keep working, and so does ksg_batch_unwind of the last batch (it removes by
+ * uid and reads out_nodes only for its sign, so the ranks in it may be the old list's). The
+ * window setting and the extension config stay. What ends is what ksg_set_cluster ends, except
+ * the pods: the static terms (call ksg_set_static_terms / ksg_add_static_config again), the
+ * window path's pods-per-window estimate, the resident server (stopped first; the next begin
+ * relaunches it). The context never takes a narrower score path than the fresh context would.
+ *
+ * Nothing is changed and the old node list stays in force for KSG_ERR_STATE (no
+ * ksg_set_cluster yet, a ksg_schedule_begin pending, a diverged context, ext given without
+ * extensions), KSG_ERR_ARG (ext NULL with extensions on, any of ksg_set_cluster's node / pair
+ * checks, old_to_new NULL with old nodes, a live pod on an outside host that is not listed,
+ * outside_old[j] below the old n_nodes or repeated, a repeated new id, a taint list out of
+ * range) and KSG_ERR_CAPACITY (shard size, max_domains, max_taints); the one visible trace of
+ * a call refused after its arguments passed is that the resident server was stopped (the next
+ * begin relaunches it). KSG_ERR_HIP marks the context diverged, as a failed batch does. On a sharded context every rank makes the same call
+ * (node state is replicated, the shard ranges are recomputed, nothing is exchanged). The pod
+ * state moves on the device (ksg_remap.hip): no pod crosses the ABI. */
+typedef struct ksg_node_ext_arrays { /* ksg_set_node_ext's arguments, for the new node list */
+  const int64_t* scalar_cap;         /* n_scalar x n_nodes */
+  const uint32_t* taint_off;
+  const uint32_t* taint_n;
+  const uint32_t* taint_ids;
+  uint32_t n_taint_ids;
+} ksg_node_ext_arrays;
+int ksg_update_cluster(ksg_ctx* ctx, const ksg_node* nodes, uint32_t n_nodes, const uint32_t* node_pairs,
+                       uint32_t n_node_pairs, const uint32_t* pair_keys, uint32_t n_pairs,
+                       const uint32_t* old_to_new, const uint32_t* outside_old, const uint32_t* outside_new,
+                       uint32_t n_outside, const ksg_node_ext_arrays* ext);
+/* Device time of the last ksg_update_cluster's remap kernels (HIP events), ms. */
+int ksg_last_update_ms(ksg_ctx* ctx, double* ms);
+/* Host time of the last ksg_update_cluster, microseconds: us3[0] validation, us3[1] the device
+ * work (the new list's tables, the remap kernels, the joined hosts' patches, the wait), us3[2]
+ * the host mirror. */
+int ksg_last_update_host_us(ksg_ctx* ctx, double* us3);
 
 /* ---- FitError reports for many pods (the batch path's FailedPredicateMap) ----
  * One device pass evaluates the predicates of n pods against every node, as

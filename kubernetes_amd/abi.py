@@ -142,6 +142,12 @@ class KsgExtConfig(C.Structure):
                 ("max_taints", U32)]
 
 
+class KsgNodeExtArrays(C.Structure):
+    """ksg_node_ext_arrays: ksg_set_node_ext's arguments for ksg_update_cluster's new node list."""
+    _fields_ = [("scalar_cap", C.c_void_p), ("taint_off", C.c_void_p), ("taint_n", C.c_void_p),
+                ("taint_ids", C.c_void_p), ("n_taint_ids", U32)]
+
+
 class KsgAdmissionSet(C.Structure):
     _fields_ = [("cap_milli_cpu", I64), ("cap_memory", I64), ("pod_off", U32), ("n_pods", U32),
                 ("label_off", U32), ("n_labels", U32)]
@@ -243,6 +249,9 @@ EXPORTS = [
     "ksg_last_explain_without_ms",
     "ksg_preempt_batch",
     "ksg_last_preempt_ms",
+    "ksg_update_cluster",
+    "ksg_last_update_ms",
+    "ksg_last_update_host_us",
 ]
 
 # int (*ksg_allgather_fn)(void* user, const void* send, void* recv, uint64_t bytes)
@@ -330,6 +339,11 @@ def load_library() -> C.CDLL:
         "ksg_last_explain_without_ms": (C.c_int, [vp, P(C.c_double)]),
         "ksg_preempt_batch": (C.c_int, [vp, vp, vp, U32, vp, U32, vp, U32, vp, U32, vp, vp, vp, vp, vp, vp]),
         "ksg_last_preempt_ms": (C.c_int, [vp, P(C.c_double)]),
+        # (ctx, nodes, n_nodes, node_pairs, n_node_pairs, pair_keys, n_pairs, old_to_new | NULL, outside_old,
+        #  outside_new, n_outside, ext | NULL)
+        "ksg_update_cluster": (C.c_int, [vp, vp, U32, vp, U32, vp, U32, vp, vp, vp, U32, P(KsgNodeExtArrays)]),
+        "ksg_last_update_ms": (C.c_int, [vp, P(C.c_double)]),
+        "ksg_last_update_host_us": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

@@ -232,6 +232,10 @@ struct ksg_ctx {
   size_t preempt_stage = (size_t)64 << 20;
   double last_preempt_ms = 0.0;
   std::vector<KsgPatch> patches;
+  // ksg_update_cluster: its remap kernels' device ms (ev0 .. ev1), and the call's host us:
+  // validation, device (build, gather, patches, the wait), host mirror
+  double last_update_ms = 0.0;
+  double last_update_us[3] = {0, 0, 0};
 
   // host mirror
   std::vector<int64_t> used_c, used_m;

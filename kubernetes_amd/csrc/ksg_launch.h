@@ -96,4 +96,17 @@ hipError_t ksg_launch_prio_merge(const KsgDev& d, uint32_t n_pods, uint32_t top,
                                  uint32_t* tie_count, uint32_t* fit_count, int32_t* top_nodes, int64_t* top_scores,
                                  hipStream_t st);
 
+// ksg_remap.hip (ksg_update_cluster): src[new_n] = the old rank behind each new rank or -1, every
+// entry below old_n (the host checks); rows are [rows][old_n] -> [rows][new_n], bitmap rows
+// [rows][old_nw] -> [rows][new_nw]. Nothing is launched for an empty grid.
+hipError_t ksg_launch_remap_rows64(const int64_t* old_rows, int64_t* new_rows, const int32_t* src, uint32_t old_n,
+                                   uint32_t new_n, uint32_t rows, hipStream_t st);
+hipError_t ksg_launch_remap_rows32(const int32_t* old_rows, int32_t* new_rows, const int32_t* src, uint32_t old_n,
+                                   uint32_t new_n, uint32_t rows, hipStream_t st);
+hipError_t ksg_launch_remap_bits(const uint64_t* old_rows, uint64_t* new_rows, const int32_t* src, uint32_t old_nw,
+                                 uint32_t new_nw, uint32_t new_n, uint32_t rows, hipStream_t st);
+hipError_t ksg_launch_remap_svc(const int32_t* new_cnt, uint32_t new_n, uint32_t n_services, const int32_t* outside_max,
+                                const int32_t* peer, const int32_t* old_total, int32_t* svc_max, int32_t* svc_total,
+                                int32_t* svc_peer, hipStream_t st);
+
 #endif  // KSG_LAUNCH_H_

@@ -1,7 +1,7 @@
 // ksg_runtime.cpp — host runtime of libkschedgpu.so: the C ABI in
 // include/kschedgpu.h except the batch entry points, the device-state mirror, the
 // RCCL exchange, the per-pod path (begin / commit / evaluate) with its resident
-// server, kubelet admission, the extensions and ksg_explain_batch. The batch driver
+// server, kubelet admission, the extensions, ksg_explain_batch and ksg_update_cluster. The batch driver
 // (ksg_schedule_batch and its variants) is ksg_batch.cpp; ksg_host.h holds what the
 // two files share (struct ksg_ctx, the scratch-buffer types, the helpers declared there).
 //
@@ -1065,15 +1065,10 @@ int ksg_destroy(ksg_ctx* c) {
 
 const char* ksg_last_error(ksg_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
-int ksg_set_cluster(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const uint32_t* node_pairs,
-                    uint32_t n_node_pairs, const uint32_t* pair_keys, uint32_t n_pairs, uint32_t n_services) {
-  if (!c) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->st));
+// ksg_set_cluster's and ksg_update_cluster's checks of the node arrays (n_pairs >= 1)
+static int check_nodes(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const uint32_t* node_pairs,
+                       uint32_t n_node_pairs, uint32_t n_pairs) {
   if (n_nodes && !nodes) return fail(c, KSG_ERR_ARG, "nodes == NULL");
-  if (n_pairs == 0) n_pairs = 1;  // pair 0 always exists (empty)
   for (uint32_t i = 0; i < n_nodes; ++i) {
     if ((size_t)nodes[i].label_off + nodes[i].n_labels > n_node_pairs)
       return fail(c, KSG_ERR_ARG, "node %u label range out of bounds", i);
@@ -1081,10 +1076,15 @@ int ksg_set_cluster(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const u
       if (node_pairs[nodes[i].label_off + k] >= n_pairs || node_pairs[nodes[i].label_off + k] == 0)
         return fail(c, KSG_ERR_ARG, "node %u has invalid pair id", i);
   }
-  free_cluster(c);
-  drop_deferred(c);
-  c->diverged = false;
-  c->ppw_est = 0.0;
+  return KSG_OK;
+}
+
+// Everything a node list determines, built into the context in fresh allocations: the shard
+// geometry, the static tables, zeroed pod-state arrays (svc_peer -1), the scratch sized for the
+// shard. The caller has put the previous list's parts away (free_cluster, or ClusterParts for
+// ksg_update_cluster); the host mirror is not touched.
+static int build_cluster(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const uint32_t* node_pairs,
+                         uint32_t n_node_pairs, const uint32_t* pair_keys, uint32_t n_pairs, uint32_t n_services) {
   c->N = n_nodes;
   c->nw = (n_nodes + 63) / 64;
   c->n_pairs = n_pairs;
@@ -1333,6 +1333,23 @@ int ksg_set_cluster(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const u
     return rc;
   HIPCHK(c, hipMemcpyAsync(c->d_shard_wlo, c->shard_wlo_h.data(), c->world * 4, hipMemcpyHostToDevice, c->st));
   HIPCHK(c, hipStreamSynchronize(c->st));
+  return KSG_OK;
+}
+
+int ksg_set_cluster(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const uint32_t* node_pairs,
+                    uint32_t n_node_pairs, const uint32_t* pair_keys, uint32_t n_pairs, uint32_t n_services) {
+  if (!c) return KSG_ERR_ARG;
+  KSG_LOCK(c);
+  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  if (n_pairs == 0) n_pairs = 1;  // pair 0 always exists (empty)
+  if (int rc = check_nodes(c, nodes, n_nodes, node_pairs, n_node_pairs, n_pairs)) return rc;
+  free_cluster(c);
+  drop_deferred(c);
+  c->diverged = false;
+  c->ppw_est = 0.0;
+  if (int rc = build_cluster(c, nodes, n_nodes, node_pairs, n_node_pairs, pair_keys, n_pairs, n_services)) return rc;
   reset_mirror(c);
   c->have_cluster = true;
   return KSG_OK;
@@ -1887,6 +1904,9 @@ int ksg_set_extensions(ksg_ctx* c, const ksg_ext_config* e) {
   return KSG_OK;
 }
 
+static int node_ext_upload(ksg_ctx* c, uint32_t n_nodes, const int64_t* scalar_cap, const uint32_t* taint_off,
+                           const uint32_t* taint_n, const uint32_t* taint_ids, uint32_t n_taint_ids);
+
 int ksg_set_node_ext(ksg_ctx* c, uint32_t n_nodes, const int64_t* scalar_cap, const uint32_t* taint_off,
                      const uint32_t* taint_n, const uint32_t* taint_ids, uint32_t n_taint_ids) {
   if (!c) return KSG_ERR_ARG;
@@ -1898,6 +1918,15 @@ int ksg_set_node_ext(ksg_ctx* c, uint32_t n_nodes, const int64_t* scalar_cap, co
   if (int rc0 = flush_deferred(c)) return rc0;
   if (!c->pods.empty()) return fail(c, KSG_ERR_STATE, "ksg_set_node_ext: call before adding pods");
   HIPCHK(c, hipSetDevice(c->device));
+  if (int rc = node_ext_upload(c, n_nodes, scalar_cap, taint_off, taint_n, taint_ids, n_taint_ids)) return rc;
+  c->sc_used.assign((size_t)c->ext.n_scalar * c->N, 0);
+  return KSG_OK;
+}
+
+// ksg_set_node_ext's arrays into the device tables of the context's node list (n_nodes == N):
+// scalar_cap, taintmap, ntaint; scalar_used zeroed
+static int node_ext_upload(ksg_ctx* c, uint32_t n_nodes, const int64_t* scalar_cap, const uint32_t* taint_off,
+                           const uint32_t* taint_n, const uint32_t* taint_ids, uint32_t n_taint_ids) {
   const size_t NN = std::max<uint32_t>(c->N, 1);
   if (c->ext.n_scalar && n_nodes) {
     if (!scalar_cap) return fail(c, KSG_ERR_ARG, "ksg_set_node_ext: scalar_cap missing");
@@ -1925,7 +1954,6 @@ int ksg_set_node_ext(ksg_ctx* c, uint32_t n_nodes, const int64_t* scalar_cap, co
   }
   HIPCHK(c, hipMemsetAsync(c->dev.scalar_used, 0, (size_t)std::max<uint32_t>(c->ext.n_scalar, 1) * NN * 8, c->st));
   HIPCHK(c, hipStreamSynchronize(c->st));
-  c->sc_used.assign((size_t)c->ext.n_scalar * c->N, 0);
   return KSG_OK;
 }
 
@@ -1939,6 +1967,341 @@ int ksg_read_ext_used(ksg_ctx* c, int64_t* used) {
   const size_t nb = (size_t)c->ext.n_scalar * c->N * 8;
   if (nb) HIPCHK(c, hipMemcpyAsync(used, c->dev.scalar_used, nb, hipMemcpyDeviceToHost, c->st));
   HIPCHK(c, hipStreamSynchronize(c->st));
+  return KSG_OK;
+}
+
+// ---- ksg_update_cluster: a new node list under the same pods (ksg_remap.hip) ------------
+// What build_cluster writes in the context. ksg_update_cluster puts the old list's parts in one
+// of these, builds the new list's beside them (the gather reads the old arrays and writes the
+// new ones), and either drops the old parts or, on any failure, swaps them back: a refused call
+// leaves the context as it was. Whatever the object holds at the end is freed with it.
+extern "C++" {
+namespace {
+struct ClusterParts {
+  uint32_t N = 0, nw = 0, n_pairs = 0, S = 0, D = 0, lo = 0, hi = 0, wlo = 0, nwords = 0, nwords_max = 0;
+  std::vector<uint32_t> shard_wlo_h;
+  int R = 1;
+  size_t lds = 0;
+  KsgDev dev{};
+  std::vector<void*> cluster_allocs;
+  DevBuf<uint32_t> d_shard_wlo;
+  DevBuf<int32_t> dbgbuf, d_dpart, d_dglobal;
+  DevBuf<uint8_t> d_fail, d_rec_send, d_rec_recv;
+  DevBuf<int64_t> d_score;
+  uint32_t rec_bytes = 0, dbg_corrupt = 0;
+  uint64_t* d_zmap = nullptr;
+  std::vector<int32_t> h_aff_pair;
+  int64_t max_cap = 0, min_cap = 0;
+  bool lr_wild = false, win_d1 = true;
+  unsigned __int128 static_mag = 0;
+  const ksg_node* d_lbl_nodes = nullptr;
+  const uint32_t* d_lbl_pairs = nullptr;
+  const uint32_t* d_lbl_keys = nullptr;
+  ~ClusterParts() {
+    for (void* p : cluster_allocs) (void)hipFree(p);
+  }
+};
+
+template <typename T>
+void swap_buf(DevBuf<T>& a, DevBuf<T>& b) {
+  std::swap(a.p, b.p);
+  std::swap(a.cap, b.cap);
+}
+
+void swap_parts(ksg_ctx* c, ClusterParts& s) {
+  std::swap(c->N, s.N);
+  std::swap(c->nw, s.nw);
+  std::swap(c->n_pairs, s.n_pairs);
+  std::swap(c->S, s.S);
+  std::swap(c->D, s.D);
+  std::swap(c->lo, s.lo);
+  std::swap(c->hi, s.hi);
+  std::swap(c->wlo, s.wlo);
+  std::swap(c->nwords, s.nwords);
+  std::swap(c->nwords_max, s.nwords_max);
+  std::swap(c->shard_wlo_h, s.shard_wlo_h);
+  std::swap(c->R, s.R);
+  std::swap(c->lds, s.lds);
+  std::swap(c->dev, s.dev);
+  std::swap(c->cluster_allocs, s.cluster_allocs);
+  swap_buf(c->d_shard_wlo, s.d_shard_wlo);
+  swap_buf(c->dbgbuf, s.dbgbuf);
+  swap_buf(c->d_dpart, s.d_dpart);
+  swap_buf(c->d_dglobal, s.d_dglobal);
+  swap_buf(c->d_fail, s.d_fail);
+  swap_buf(c->d_rec_send, s.d_rec_send);
+  swap_buf(c->d_rec_recv, s.d_rec_recv);
+  swap_buf(c->d_score, s.d_score);
+  std::swap(c->rec_bytes, s.rec_bytes);
+  std::swap(c->dbg_corrupt, s.dbg_corrupt);
+  std::swap(c->d_zmap, s.d_zmap);
+  std::swap(c->h_aff_pair, s.h_aff_pair);
+  std::swap(c->max_cap, s.max_cap);
+  std::swap(c->min_cap, s.min_cap);
+  std::swap(c->lr_wild, s.lr_wild);
+  std::swap(c->win_d1, s.win_d1);
+  std::swap(c->static_mag, s.static_mag);
+  std::swap(c->d_lbl_nodes, s.d_lbl_nodes);
+  std::swap(c->d_lbl_pairs, s.d_lbl_pairs);
+  std::swap(c->d_lbl_keys, s.d_lbl_keys);
+}
+
+// the host mirror of the new list, computed beside the old one and installed after the device work
+struct NewMirror {
+  std::vector<int64_t> used_c, used_m, sc_used;
+  std::vector<int32_t> svc_cnt, svc_max, svc_peer, outside_max;
+  std::unordered_map<uint64_t, uint32_t> key_ref;
+  std::vector<std::unordered_map<uint32_t, int32_t>> svc_ext;
+  std::vector<std::map<uint64_t, uint32_t>> svc_members;
+  std::vector<std::pair<PodRec*, uint32_t>> moved;  // pods whose host id changes
+};
+
+double us_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+}
+}  // namespace
+}  // extern "C++"
+
+// The device half, with the new list's arrays in c->dev and the old list's in old.dev: the
+// gather by src, the svc kernel, then the joined hosts' pods as patches (nm has their values).
+static int remap_device(ksg_ctx* c, const ClusterParts& old, const std::vector<int32_t>& src, const NewMirror& nm) {
+  const uint32_t N = c->N, S = c->S, K = c->cfg.max_conflict_keys;
+  struct Scratch {
+    int32_t* p = nullptr;
+    ~Scratch() {
+      if (p) (void)hipFree(p);
+    }
+  } tmp;
+  const size_t words = (size_t)N + 2 * (size_t)S;
+  HIPCHK(c, hipMalloc((void**)&tmp.p, std::max<size_t>(words, 1) * sizeof(int32_t)));
+  int32_t *d_src = tmp.p, *d_omax = tmp.p + N, *d_peer = d_omax + S;
+  if (N) HIPCHK(c, hipMemcpyAsync(d_src, src.data(), (size_t)N * 4, hipMemcpyHostToDevice, c->st));
+  if (S) {
+    HIPCHK(c, hipMemcpyAsync(d_omax, nm.outside_max.data(), (size_t)S * 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemcpyAsync(d_peer, nm.svc_peer.data(), (size_t)S * 4, hipMemcpyHostToDevice, c->st));
+  }
+  const KsgDev &o = old.dev, &d = c->dev;
+  HIPCHK(c, hipEventRecord(c->ev0, c->st));
+  HIPCHK(c, ksg_launch_remap_rows64(o.used_cpu, d.used_cpu, d_src, old.N, N, 1, c->st));
+  HIPCHK(c, ksg_launch_remap_rows64(o.used_mem, d.used_mem, d_src, old.N, N, 1, c->st));
+  if (c->ext_on && c->ext.n_scalar)
+    HIPCHK(c, ksg_launch_remap_rows64(o.scalar_used, d.scalar_used, d_src, old.N, N, c->ext.n_scalar, c->st));
+  HIPCHK(c, ksg_launch_remap_rows32(o.svc_cnt, d.svc_cnt, d_src, old.N, N, S, c->st));
+  HIPCHK(c, ksg_launch_remap_bits(o.keymap, d.keymap, d_src, old.nw, c->nw, N, K, c->st));
+  HIPCHK(c, ksg_launch_remap_bits(o.svc_bits, d.svc_bits, d_src, old.nw, c->nw, N, S, c->st));
+  HIPCHK(c, ksg_launch_remap_svc(d.svc_cnt, N, S, d_omax, d_peer, o.svc_total, d.svc_max, d.svc_total, d.svc_peer, c->st));
+  HIPCHK(c, hipEventRecord(c->ev1, c->st));
+  if (int rc = flush_patches(c)) return rc;  // (the joined hosts' pods; synchronises when there are any)
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  float ms = 0.f;
+  HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  c->last_update_ms = ms;
+  return KSG_OK;
+}
+
+static int update_cluster_impl(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const uint32_t* node_pairs,
+                               uint32_t n_node_pairs, const uint32_t* pair_keys, uint32_t n_pairs,
+                               const uint32_t* old_to_new, const uint32_t* outside_old, const uint32_t* outside_new,
+                               uint32_t n_outside, const ksg_node_ext_arrays* ext) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (int rs = cluster_ok(c)) return rs;
+  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
+  if (ext && !c->ext_on) return fail(c, KSG_ERR_STATE, "ksg_update_cluster: ext given, extensions are off");
+  if (!ext && c->ext_on) return fail(c, KSG_ERR_ARG, "ksg_update_cluster: extensions are on, ext == NULL");
+  // (what the arguments alone decide comes first: such a refusal does not even stop the server)
+  if (n_pairs == 0) n_pairs = 1;  // pair 0 always exists (empty)
+  if (int rc = check_nodes(c, nodes, n_nodes, node_pairs, n_node_pairs, n_pairs)) return rc;
+  const uint32_t oldN = c->N, S = c->S;
+  if (n_nodes > (uint32_t)INT32_MAX) return fail(c, KSG_ERR_CAPACITY, "ksg_update_cluster: %u nodes", n_nodes);
+  if (oldN && !old_to_new) return fail(c, KSG_ERR_ARG, "ksg_update_cluster: old_to_new == NULL with %u old nodes", oldN);
+  if (n_outside && (!outside_old || !outside_new))
+    return fail(c, KSG_ERR_ARG, "ksg_update_cluster: outside arrays missing");
+  // the renaming: injective over the old ranks and the listed outside hosts
+  std::unordered_map<uint32_t, uint32_t> omap;
+  std::unordered_set<uint32_t> taken;
+  omap.reserve(n_outside);
+  taken.reserve((size_t)oldN + n_outside);
+  for (uint32_t r = 0; r < oldN; ++r)
+    if (!taken.insert(old_to_new[r]).second)
+      return fail(c, KSG_ERR_ARG, "ksg_update_cluster: new host id %u given twice", old_to_new[r]);
+  for (uint32_t j = 0; j < n_outside; ++j) {
+    if (outside_old[j] < oldN)
+      return fail(c, KSG_ERR_ARG, "ksg_update_cluster: outside_old[%u] = %u is a rank of the old list", j, outside_old[j]);
+    if (!omap.emplace(outside_old[j], outside_new[j]).second)
+      return fail(c, KSG_ERR_ARG, "ksg_update_cluster: outside host %u listed twice", outside_old[j]);
+    if (!taken.insert(outside_new[j]).second)
+      return fail(c, KSG_ERR_ARG, "ksg_update_cluster: new host id %u given twice", outside_new[j]);
+  }
+  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
+  HIPCHK(c, hipSetDevice(c->device));
+  // the mirror is complete and the device equals it
+  if (int rc = flush_deferred(c)) return rc;
+  if (int rc = flush_patches(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  for (const auto& kv : c->pods)
+    if (kv.second.host >= oldN && !omap.count(kv.second.host))
+      return fail(c, KSG_ERR_ARG, "ksg_update_cluster: pod %llu is on outside host %u, which is not listed",
+                  (unsigned long long)kv.first, kv.second.host);
+  // src: the old rank behind each new rank (every entry < oldN, so no kernel reads outside a row)
+  std::vector<int32_t> src(n_nodes, -1);
+  for (uint32_t r = 0; r < oldN; ++r)
+    if (old_to_new[r] < n_nodes) src[old_to_new[r]] = (int32_t)r;
+  auto renamed = [&](uint32_t h) { return h < oldN ? old_to_new[h] : omap.find(h)->second; };
+  const double us_valid = us_since(t0);
+
+  // ---- the new list's tables beside the old one's ----
+  const auto t1 = std::chrono::steady_clock::now();
+  ClusterParts old;
+  swap_parts(c, old);
+  auto refuse = [&](int rc) {
+    swap_parts(c, old);  // (the new list's parts leave with `old`)
+    c->patches.clear();
+    return rc;
+  };
+  if (int rc = build_cluster(c, nodes, n_nodes, node_pairs, n_node_pairs, pair_keys, n_pairs, S)) return refuse(rc);
+  if (ext)
+    if (int rc = node_ext_upload(c, n_nodes, ext->scalar_cap, ext->taint_off, ext->taint_n, ext->taint_ids, ext->n_taint_ids))
+      return refuse(rc);
+
+  // ---- the new mirror: survivors' rows by src, then one walk over the pods ----
+  const auto t2 = std::chrono::steady_clock::now();
+  const uint32_t N = n_nodes, nsc = c->ext_on ? c->ext.n_scalar : 0;
+  NewMirror nm;
+  nm.used_c.assign(N, 0);
+  nm.used_m.assign(N, 0);
+  nm.sc_used.assign((size_t)c->ext.n_scalar * N, 0);
+  nm.svc_cnt.assign((size_t)S * N, 0);
+  nm.svc_max.assign(S, 0);
+  nm.outside_max.assign(S, 0);
+  nm.svc_peer.assign(S, -1);
+  nm.svc_ext.assign(S, {});
+  nm.svc_members.assign(S, {});
+  for (uint32_t n = 0; n < N; ++n)
+    if (src[n] >= 0) {
+      nm.used_c[n] = c->used_c[src[n]];
+      nm.used_m[n] = c->used_m[src[n]];
+    }
+  for (uint32_t q = 0; q < nsc; ++q)
+    for (uint32_t n = 0; n < N; ++n)
+      if (src[n] >= 0) nm.sc_used[(size_t)q * N + n] = c->sc_used[(size_t)q * oldN + src[n]];
+  for (uint32_t s = 0; s < S; ++s) {
+    const int32_t* from = c->svc_cnt.data() + (size_t)s * oldN;
+    int32_t* to = nm.svc_cnt.data() + (size_t)s * N;
+    int32_t m = 0;
+    for (uint32_t n = 0; n < N; ++n)
+      if (src[n] >= 0) m = std::max(m, to[n] = from[src[n]]);
+    nm.svc_max[s] = m;
+  }
+  nm.key_ref.reserve(c->key_ref.size());
+  for (const auto& kv : c->key_ref) {
+    const uint32_t t = old_to_new[(uint32_t)kv.first];
+    if (t < N) nm.key_ref[(kv.first & 0xffffffff00000000ull) | t] = kv.second;
+  }
+  const KsgDev& d = c->dev;
+  bool joined_wild = false;         // a joined host's pod would have set lr_wild in the fresh context
+  int64_t joined_hi = c->used_hi;   // ... and the largest total it would have seen (used_hi only grows)
+  for (auto& kv : c->pods) {
+    PodRec& r = kv.second;
+    const uint32_t t = renamed(r.host);
+    if (t != r.host) nm.moved.emplace_back(&r, t);
+    if (t >= N) {  // outside the new list: counted by svc_max alone
+      for (uint32_t s : r.svcs) nm.outside_max[s] = std::max(nm.outside_max[s], ++nm.svc_ext[s][t]);
+      continue;
+    }
+    if (r.host < oldN) continue;  // (a survivor: its rows were gathered)
+    // a host that joined the list: its pods onto the node, as mirror_add would (values for the patches).
+    // On an outside host note_requests never saw them (ksg_add_pod checks node hosts only); the fresh
+    // context re-adds them on a node, so a negative request or a total that could wrap turns it wide.
+    joined_wild = joined_wild || r.cpu < 0 || r.mem < 0 ||
+                  (unsigned __int128)(uint64_t)std::max<int64_t>(joined_hi, 0) + (uint64_t)std::max<int64_t>(std::max(r.cpu, r.mem), 0) >
+                      (unsigned __int128)INT64_MAX;
+    nm.used_c[t] = (int64_t)((uint64_t)nm.used_c[t] + (uint64_t)r.cpu);
+    nm.used_m[t] = (int64_t)((uint64_t)nm.used_m[t] + (uint64_t)r.mem);
+    joined_hi = std::max(joined_hi, std::max(nm.used_c[t], nm.used_m[t]));
+    patch64(c, d.used_cpu + t, nm.used_c[t]);
+    patch64(c, d.used_mem + t, nm.used_m[t]);
+    for (uint32_t q = 0; q < nsc; ++q) {
+      if (!r.scalar[q]) continue;
+      int64_t& u = nm.sc_used[(size_t)q * N + t];
+      u = (int64_t)((uint64_t)u + (uint64_t)r.scalar[q]);
+      patch64(c, d.scalar_used + (size_t)q * N + t, u);
+    }
+    for (uint32_t k : r.keys)
+      if (++nm.key_ref[((uint64_t)k << 32) | t] == 1) patch_or(c, d.keymap + (size_t)k * c->nw + (t >> 6), 1ULL << (t & 63));
+    for (uint32_t s : r.svcs) {
+      const int32_t v = ++nm.svc_cnt[(size_t)s * N + t];
+      patch32(c, d.svc_cnt + (size_t)s * N + t, v);
+      if (v == 1) patch_or(c, d.svc_bits + (size_t)s * c->nw + (t >> 6), 1ULL << (t & 63));
+      nm.svc_max[s] = std::max(nm.svc_max[s], v);
+    }
+  }
+  for (uint32_t s = 0; s < S; ++s) {
+    for (const auto& m : c->svc_members[s]) nm.svc_members[s].emplace_hint(nm.svc_members[s].end(), m.first, renamed(m.second));
+    if (!nm.svc_members[s].empty()) {
+      const uint32_t h = nm.svc_members[s].begin()->second;
+      nm.svc_peer[s] = h < N ? (int32_t)h : -2;
+    }
+    nm.svc_max[s] = std::max(nm.svc_max[s], nm.outside_max[s]);
+  }
+  // (the svc kernel sees the gathered counts only: the joined hosts' maxima go with their patches)
+  if (!c->patches.empty())
+    for (uint32_t s = 0; s < S; ++s) patch32(c, d.svc_max + s, nm.svc_max[s]);
+  double us_mirror = us_since(t2);
+
+  // ---- the device work; then the new list is in force ----
+  const auto t3 = std::chrono::steady_clock::now();
+  if (int rc = remap_device(c, old, src, nm)) return refuse(rc);
+  const double us_dev = std::chrono::duration<double, std::micro>(t2 - t1).count() + us_since(t3);
+  const auto t4 = std::chrono::steady_clock::now();
+  for (auto& mv : nm.moved) mv.first->host = mv.second;
+  c->used_c = std::move(nm.used_c);
+  c->used_m = std::move(nm.used_m);
+  c->sc_used = std::move(nm.sc_used);
+  c->svc_cnt = std::move(nm.svc_cnt);
+  c->svc_max = std::move(nm.svc_max);
+  c->svc_peer = std::move(nm.svc_peer);
+  c->key_ref = std::move(nm.key_ref);
+  c->svc_ext = std::move(nm.svc_ext);
+  c->svc_members = std::move(nm.svc_members);
+  // the score path: never narrower than the fresh context's (the sticky causes stay, the
+  // capacities' were recomputed by build_cluster, the used-total bounds are recomputed on use)
+  c->lr_wild = c->lr_wild || old.lr_wild || joined_wild;
+  c->used_hi = std::max(c->used_hi, joined_hi);
+  for (uint32_t n = 0; n < N; ++n) c->used_hi = std::max(c->used_hi, std::max(c->used_c[n], c->used_m[n]));
+  c->mu_dirty = true;
+  set_wide(c);
+  c->ppw_est = 0.0;
+  us_mirror += us_since(t4);
+  c->last_update_us[0] = us_valid;
+  c->last_update_us[1] = us_dev;
+  c->last_update_us[2] = us_mirror;
+  return KSG_OK;
+}
+
+int ksg_update_cluster(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const uint32_t* node_pairs,
+                       uint32_t n_node_pairs, const uint32_t* pair_keys, uint32_t n_pairs, const uint32_t* old_to_new,
+                       const uint32_t* outside_old, const uint32_t* outside_new, uint32_t n_outside,
+                       const ksg_node_ext_arrays* ext) {
+  if (!c) return KSG_ERR_ARG;
+  KSG_LOCK(c);
+  const int rc = update_cluster_impl(c, nodes, n_nodes, node_pairs, n_node_pairs, pair_keys, n_pairs, old_to_new,
+                                     outside_old, outside_new, n_outside, ext);
+  // a HIP error at any point: the device may not be what the mirror says (as after a failed batch)
+  if (rc == KSG_ERR_HIP && c->have_cluster) c->diverged = true;
+  return rc;
+}
+
+int ksg_last_update_ms(ksg_ctx* c, double* ms) {
+  if (!c || !ms) return KSG_ERR_ARG;
+  KSG_LOCK(c);
+  *ms = c->last_update_ms;
+  return KSG_OK;
+}
+
+int ksg_last_update_host_us(ksg_ctx* c, double* us3) {
+  if (!c || !us3) return KSG_ERR_ARG;
+  KSG_LOCK(c);
+  for (int i = 0; i < 3; ++i) us3[i] = c->last_update_us[i];
   return KSG_OK;
 }
 

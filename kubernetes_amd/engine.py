@@ -149,6 +149,52 @@ class DeviceScheduler:
         self.n_nodes = len(nodes)
         self.n_services = int(cl.n_services)
 
+    def update_cluster(self, cl: ClusterArrays, old_to_new, outside=(), node_ext=None):
+        """ksg_update_cluster: `cl` replaces the node list and every live pod stays, on its renamed
+        host. old_to_new[r] = the host id of old node r's pods now (>= len(cl.nodes): the node left);
+        outside = (old id, new id) pairs of the hosts outside the old list (ClusterView.host_map
+        builds both); node_ext = set_node_ext's (scalar_cap, taint_off, taint_n, taint_ids) for the
+        new list, required exactly when the context has extensions. The service count must not have
+        changed; the static terms end (set_static_terms / add_static_config again)."""
+        nodes = np.ascontiguousarray(cl.nodes, dtype=abi.NODE_DTYPE)
+        np_ = _u32(cl.node_pairs if len(cl.node_pairs) else np.zeros(1, np.uint32))
+        pk = _u32(cl.pair_keys if len(cl.pair_keys) else np.zeros(1, np.uint32))
+        o2n = _u32(old_to_new)
+        if len(o2n) != self.n_nodes:
+            raise ValueError(f"old_to_new has {len(o2n)} entries for {self.n_nodes} old nodes")
+        if int(cl.n_services) != self.n_services:
+            raise ValueError("update_cluster keeps the service list: a changed one needs set_cluster")
+        out = np.asarray(list(outside), dtype=np.uint32).reshape(-1, 2)
+        oo, on = _u32(out[:, 0]), _u32(out[:, 1])
+        ext = None
+        if node_ext is not None:
+            scalar_cap, taint_off, taint_n, taint_ids = node_ext
+            cap = np.ascontiguousarray(scalar_cap, np.int64).reshape(-1)
+            cap = cap if len(cap) else np.zeros(1, np.int64)
+            ti = _u32(taint_ids if len(taint_ids) else np.zeros(1, np.uint32))
+            toff, tn = _u32(taint_off), _u32(taint_n)  # (held: a converted copy must outlive the call)
+            ext = abi.KsgNodeExtArrays(cap.ctypes.data, toff.ctypes.data if len(toff) else None,
+                                       tn.ctypes.data if len(tn) else None, ti.ctypes.data, len(taint_ids))
+        rc = self._lib.ksg_update_cluster(self._ctx, abi.ptr(nodes), len(nodes), abi.ptr(np_), len(cl.node_pairs),
+                                          abi.ptr(pk), len(pk), abi.ptr(o2n) if len(o2n) else None,
+                                          abi.ptr(oo) if len(oo) else None, abi.ptr(on) if len(on) else None, len(oo),
+                                          C.byref(ext) if ext is not None else None)
+        if rc != abi.KSG_OK:
+            self._err(rc)
+        self.n_nodes = len(nodes)
+
+    def last_update_ms(self) -> float:
+        """Device ms of the last update_cluster's remap kernels."""
+        ms = C.c_double(0.0)
+        self._lib.ksg_last_update_ms(self._ctx, C.byref(ms))
+        return ms.value
+
+    def last_update_host_us(self) -> dict:
+        """Host microseconds of the last update_cluster by phase."""
+        out = np.zeros(3, np.float64)
+        self._lib.ksg_last_update_host_us(self._ctx, abi.ptr(out))
+        return {"validate": float(out[0]), "device": float(out[1]), "mirror": float(out[2])}
+
     # ---- extensions (include/kschedgpu.h; parity unpinned) ---------------------
     def set_extensions(self, ext: abi.KsgExtConfig):
         rc = self._lib.ksg_set_extensions(self._ctx, C.byref(ext))

@@ -119,6 +119,26 @@ class ClusterView:
             ext[host] = len(ext)
         return len(self.names) + ext[host]
 
+    def host_map(self, old: "ClusterView"):
+        """The host renaming DeviceScheduler.update_cluster takes when this view replaces `old`
+        (same interner) -> (old_to_new, outside_pairs). Survivors are matched by node name; a node
+        that left gets this view's outside id for its name; every host name the interner knows
+        outside a node list, old id len(old.names) + e, maps to its rank here if it joined the
+        list and to len(self.names) + e otherwise. (The interner never forgets a host name, so the
+        pairs grow with the names ever seen outside a list, not with the hosts that still hold pods:
+        a caller with many short-lived node names lists only the hosts its pods are on.)"""
+        if old.interner is not self.interner:
+            raise ValueError("host_map: the two views must share one Interner")
+        old_to_new = np.asarray([self.host_id(name) for name in old.names], dtype=np.uint32)
+        n_old, n_new = len(old.names), len(self.names)
+        outside = []
+        for name, e in self.interner.ext_hosts.items():
+            if name in old.rank:  # (it was a node of the old list: old_to_new renames it)
+                continue
+            r = self.rank.get(name)
+            outside.append((n_old + e, r if r is not None else n_new + e))
+        return old_to_new, outside
+
     def pod_services(self, pod: Pod) -> List[int]:
         """Indices (service-list order) of the services selecting the pod: same
         namespace, selector matches its labels (GetPodServices, listers.go:63-91)."""

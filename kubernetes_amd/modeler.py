@@ -199,7 +199,8 @@ class PodMirror:
         self.pending: Dict[str, Tuple[int, int]] = {}  # key -> (uid, host_id) of our own commits
         modeler.scheduled_pods.store.add_listener(self._listener(self.SCHED))
         modeler.assumed_pods.store.add_listener(self._listener(self.ASSUMED))
-        self.stats = {"adds": 0, "removes": 0, "adopted": 0, "dropped_commits": 0, "reloads": 0}
+        self.stats = {"adds": 0, "removes": 0, "adopted": 0, "dropped_commits": 0, "reloads": 0,
+                      "rehosts": 0}
 
     def _listener(self, src: int):
         def fn(op, key, old, new):
@@ -274,6 +275,13 @@ class PodMirror:
             if ok:
                 self._add(src, key, p)
         self.stats["reloads"] += 1
+
+    def rehost(self, fn: Callable[[int], int]) -> None:
+        """The node list changed under the same pods (DeviceScheduler.update_cluster): the
+        device kept every uid, so `on_device` and the queue stay, and only the host ids held for
+        our own commits are renamed by fn(old id) -> new id."""
+        self.pending = {k: (uid, fn(h)) for k, (uid, h) in self.pending.items()}
+        self.stats["rehosts"] = self.stats.get("rehosts", 0) + 1
 
     def committed(self, pod: Pod, uid: int, host_id: int) -> None:
         key = meta_namespace_key(pod)

@@ -115,8 +115,11 @@ class GPUScheduler:
     """algorithm.Scheduler on the MI355X (NewGenericScheduler's drop-in)."""
 
     def __init__(self, config: SchedulerConfig, pod_lister, service_lister=None, random=None,
-                 device: int = 0):
+                 device: int = 0, incremental_nodes: bool = False):
         self.config = config
+        # a changed node list under an unchanged service list keeps the device's pods
+        # (DeviceScheduler.update_cluster) instead of resetting and re-adding every one
+        self.incremental_nodes = incremental_nodes
         self.pod_lister = pod_lister
         self.service_lister = service_lister or FakeServiceLister([])
         self.random = random if random is not None else SplitMix64Rand(0)
@@ -159,6 +162,24 @@ class GPUScheduler:
         # 5k nodes (an equal-valued replacement object counts as unchanged)
         nsig = list(nodes)
         ssig = list(services)
+        if self.incremental_nodes and self.view is not None and ssig == self._svc_sig and nsig != self._node_sig:
+            old = self.view
+            view = ClusterView(nodes, services, self.interner)
+            old_to_new, outside = view.host_map(old)
+            self.engine.update_cluster(view.arrays, old_to_new, outside)
+            self.view = view
+            for extra in self.config.static_passes(self.interner.key_id):
+                self.engine.add_static_config(extra)
+            self._node_sig = nsig
+            ren = dict(outside)
+
+            def fn(h, n_old=len(old.names)):
+                return int(old_to_new[h]) if h < n_old else ren.get(h, h)
+
+            self._mirror = {k: (uid, fn(h), pid) for k, (uid, h, pid) in self._mirror.items()}
+            self._assumed = [(k, uid, fn(h)) for k, uid, h in self._assumed]
+            if self._events is not None:
+                self._events.rehost(fn)
         if nsig != self._node_sig or ssig != self._svc_sig or self.view is None:
             self.view = ClusterView(nodes, services, self.interner)
             self.engine.set_cluster(self.view.arrays)
