@@ -25,11 +25,11 @@ namespace {
 // from wrapping (ServiceAntiAffinity is handled by its count pass and stops).
 // The resolver walks the whole node set on every rank (state is replicated).
 KsgDev full_geometry(const ksg_ctx* c) {
-  KsgDev f = c->dev;
+  KsgDev f = c->cl.dev;
   f.lo = 0;
-  f.hi = c->N;
+  f.hi = c->cl.N;
   f.wlo = 0;
-  f.nwords = c->nw;
+  f.nwords = c->cl.nw;
   return f;
 }
 
@@ -42,7 +42,7 @@ int64_t win_request(const ksg_pod& p) {
 }
 
 bool use_window(ksg_ctx* c, const ksg_pod* pods, uint32_t n) {
-  if (c->window == 0 || c->nw > 32 * 64 || ksg_win_max_window(full_geometry(c)) < 8) return false;
+  if (c->window == 0 || c->cl.nw > 32 * 64 || ksg_win_max_window(full_geometry(c)) < 8) return false;
   // extensions: PodToleratesNodeTaints is static per (pod, node); extended
   // resources only shrink under commits and the resolver re-checks them on the
   // window's committed nodes like cpu / memory. With TaintToleration /
@@ -58,7 +58,7 @@ bool use_window(ksg_ctx* c, const ksg_pod* pods, uint32_t n) {
     // resolvers re-check nothing extension-specific on the window's committed nodes
     const bool anti = anti_on(c);
     if (anti && (c->ext.w_taint_toleration != 0 || c->ext.w_balanced != 0)) return false;
-    if (c->ext.w_taint_toleration != 0 && !c->dev.ntaint) return false;
+    if (c->ext.w_taint_toleration != 0 && !c->cl.dev.ntaint) return false;
     if (c->cur_ext)
       for (uint32_t i = 0; i < n; ++i)
         for (uint32_t r = 0; r < c->ext.n_scalar; ++r) {
@@ -68,17 +68,17 @@ bool use_window(ksg_ctx* c, const ksg_pod* pods, uint32_t n) {
         }
   }
   // int64 combined scores
-  if (c->dev.wide) return false;
+  if (c->cl.dev.wide) return false;
   // monotonicity under commits needs non-negative pod-dependent weights
   if (c->cfg.w_least_requested < 0 || c->cfg.w_service_spreading < 0) return false;
   const int64_t lim = KSG_WIN_LR_BOUND;
-  if (c->max_cap > lim || c->min_cap < 0) return false;
+  if (c->cl.max_cap > lim || c->cl.min_cap < 0) return false;
   if (c->mu_dirty) {
     c->mu_max = 0;
     c->mu_neg = false;
-    for (uint32_t i = 0; i < c->N; ++i) {
-      c->mu_neg |= c->used_c[i] < 0 || c->used_m[i] < 0;
-      c->mu_max = std::max<int64_t>(c->mu_max, std::max<int64_t>(c->used_c[i], c->used_m[i]));
+    for (uint32_t i = 0; i < c->cl.N; ++i) {
+      c->mu_neg |= c->mir.used_c[i] < 0 || c->mir.used_m[i] < 0;
+      c->mu_max = std::max<int64_t>(c->mu_max, std::max<int64_t>(c->mir.used_c[i], c->mir.used_m[i]));
     }
     c->mu_dirty = false;
   }
@@ -215,15 +215,15 @@ int batch_begin(ksg_ctx* c, BatchRun& run, const uint64_t* rng_state, const ksg_
 // off, one pod when the window path met a pod whose id lists exceed the window record.
 int exact_pods(ksg_ctx* c, uint32_t first, uint32_t count, const ksg_pod_ext* dext) {
   if (!c->xchg) {
-    HIPCHK(c, ksg_launch_batch(c->R, anti_on(c), c->dev, c->d_pods + first, c->d_ids, count, c->d_rng,
+    HIPCHK(c, ksg_launch_batch(c->cl.R, anti_on(c), c->cl.dev, c->d_pods + first, c->d_ids, count, c->d_rng,
                                c->d_out + first, c->st, dext ? dext + first : nullptr));
     return KSG_OK;
   }
   for (uint32_t i = first; i < first + count; ++i) {
     if (int rc = scan_exchange(c, c->d_pods + i, c->d_ids, KSG_MODE_BEGIN, nullptr, nullptr, dext ? dext + i : nullptr))
       return rc;
-    HIPCHK(c, ksg_launch_decide(c->dev, c->d_pods + i, c->d_ids, rec_buf(c), c->rec_bytes, c->world,
-                                c->d_shard_wlo, 1, 0, c->d_rng, c->d_out, i, c->d_summary, c->st,
+    HIPCHK(c, ksg_launch_decide(c->cl.dev, c->d_pods + i, c->d_ids, rec_buf(c), c->cl.rec_bytes, c->world,
+                                c->cl.d_shard_wlo, 1, 0, c->d_rng, c->d_out, i, c->d_summary, c->st,
                                 dext ? dext + i : nullptr));
   }
   return KSG_OK;
@@ -285,17 +285,17 @@ int win_plan(ksg_ctx* c, uint32_t n, const ksg_pod_ext* dext, WinPlan* pl) {
   KsgWinXchg& x = pl->x;
   x = KsgWinXchg{};
   x.exts = dext;  // (extensions: the filters, and the scores when esc)
-  x.ostride = std::max<uint32_t>(c->nwords_max, 1);
+  x.ostride = std::max<uint32_t>(c->cl.nwords_max, 1);
   x.wcap = W;
   x.world = (uint32_t)c->world;
   for (int g = 0; g < c->world; ++g) {
     uint32_t a, b;
-    ksg_shard_words(c->nw, (uint32_t)g, (uint32_t)c->world, &a, &b);
+    ksg_shard_words(c->cl.nw, (uint32_t)g, (uint32_t)c->world, &a, &b);
     x.wlo[g] = a;
     x.nw[g] = b - a;
   }
   const bool anti = pl->anti = anti_on(c);
-  const bool rr = pl->rr = anti && c->dev.rr_dz != 0 && c->d_zmap;  // ServiceAntiAffinity re-rank
+  const bool rr = pl->rr = anti && c->cl.dev.rr_dz != 0 && c->cl.d_zmap;  // ServiceAntiAffinity re-rank
   const size_t fit_off = pl->fit_off = ((size_t)W * x.ostride * 12 + 7) & ~(size_t)7;
   // (the domain counts are zeroed once here, then by each resolver for the next window)
   x.fit_off = anti ? (uint32_t)fit_off : 0u;
@@ -307,7 +307,7 @@ int win_plan(ksg_ctx* c, uint32_t n, const ksg_pod_ext* dext, WinPlan* pl) {
   x.efit_off = esc ? (uint32_t)fit_off : 0u;
   // the plain resolver without extensions up to 16,384 nodes (its ring holds the bitmaps):
   // phase A's single-commit drop bitmaps at the same offset
-  const bool d1 = pl->d1 = !anti && !dext && c->win_d1 && c->nw <= 4 * 64;
+  const bool d1 = pl->d1 = !anti && !dext && c->cl.win_d1 && c->cl.nw <= 4 * 64;
   x.d1 = d1 ? 1u : 0u;
   x.d1_off = d1 ? (uint32_t)fit_off : 0u;
   x.blk = ((rr                  ? fit_off + (size_t)W * x.ostride * 16
@@ -325,7 +325,7 @@ int win_plan(ksg_ctx* c, uint32_t n, const ksg_pod_ext* dext, WinPlan* pl) {
     x.thist = c->d_ethist;
     x.psoft = c->d_epsoft;
   }
-  const size_t dcnt_n = pl->dcnt_n = (size_t)W * std::max<uint32_t>(c->D, 1);
+  const size_t dcnt_n = pl->dcnt_n = (size_t)W * std::max<uint32_t>(c->cl.D, 1);
   if (anti) {
     if ((rc = c->d_dcnt.grow(c, dcnt_n))) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_dcnt, 0, dcnt_n * sizeof(int32_t), c->st));
@@ -333,14 +333,14 @@ int win_plan(ksg_ctx* c, uint32_t n, const ksg_pod_ext* dext, WinPlan* pl) {
     x.dcnt_n = (uint32_t)dcnt_n;
   }
   if (rr) {  // (the resolver resets the row bests to KSG_S32_NONE and the B counts to 0 for the next window)
-    const size_t dmb_n = (size_t)W * c->dev.rr_dz;  // [W][dz] row bests, then [W][dz] B nodes per row
+    const size_t dmb_n = (size_t)W * c->cl.dev.rr_dz;  // [W][dz] row bests, then [W][dz] B nodes per row
     if ((rc = c->d_dmb.grow(c, 2 * dmb_n))) return rc;
     HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->d_dmb.p, (int)0x80000000, dmb_n, c->st));
     HIPCHK(c, hipMemsetAsync(c->d_dmb + dmb_n, 0, dmb_n * sizeof(int32_t), c->st));
     x.rr = 1;
-    x.dz = c->dev.rr_dz;
+    x.dz = c->cl.dev.rr_dz;
     x.dmb = c->d_dmb;
-    x.zmap = c->d_zmap;
+    x.zmap = c->cl.d_zmap;
   }
   if ((rc = c->d_winsum.grow(c, W))) return rc;
   if ((rc = c->d_xsend.grow(c, x.blk))) return rc;
@@ -410,12 +410,12 @@ int win_enqueue_round(ksg_ctx* c, const WinPlan& pl, uint32_t pos, uint32_t n, u
     if (pl.anti) {
       // ServiceAntiAffinity: the pods' per-domain counts over their filtered nodes first
       // (into d_dcnt, zero: the previous resolver cleared it)
-      HIPCHK(c, ksg_launch_win_eval(c->dev, 1, c->d_pods, c->d_ids, c->d_run, W, c->d_winsum, pl.wbits, pl.wmax,
+      HIPCHK(c, ksg_launch_win_eval(c->cl.dev, 1, c->d_pods, c->d_ids, c->d_run, W, c->d_winsum, pl.wbits, pl.wmax,
                                     x.ostride, c->d_dcnt, nullptr, x.dmb, nullptr, x.dz, c->st, pl.dext));
       if (c->xchg && (rc = allreduce_i32(c, Reduce::Sum, c->d_dcnt, c->d_dcnt, (uint32_t)pl.dcnt_n))) return rc;
     }
     if (pl.etm) {  // TaintToleration: each pod's max soft-taint count over its filtered nodes first
-      HIPCHK(c, ksg_launch_win_eval(c->dev, 3, c->d_pods, c->d_ids, c->d_run, W, c->d_winsum, pl.wbits, pl.wmax,
+      HIPCHK(c, ksg_launch_win_eval(c->cl.dev, 3, c->d_pods, c->d_ids, c->d_run, W, c->d_winsum, pl.wbits, pl.wmax,
                                     x.ostride, nullptr, nullptr, nullptr, nullptr, 0, c->st, pl.dext, x.tmax,
                                     x.psoft, x.thist));
       // sharded: over every shard's filtered nodes (the max, and the histogram of soft
@@ -424,7 +424,7 @@ int win_enqueue_round(ksg_ctx* c, const WinPlan& pl, uint32_t pos, uint32_t n, u
                       (rc = allreduce_i32(c, Reduce::Sum, x.thist, x.thist, W * KSG_TBINS))))
         return rc;
     }
-    HIPCHK(c, ksg_launch_win_eval(c->dev, pl.anti ? 2 : 0, c->d_pods, c->d_ids, c->d_run, W, c->d_winsum, pl.wbits,
+    HIPCHK(c, ksg_launch_win_eval(c->cl.dev, pl.anti ? 2 : 0, c->d_pods, c->d_ids, c->d_run, W, c->d_winsum, pl.wbits,
                                   pl.wmax, x.ostride, c->d_dcnt,
                                   (pl.anti || pl.esc || pl.d1) ? reinterpret_cast<uint64_t*>(c->d_xsend + pl.fit_off)
                                                                : nullptr,
@@ -589,7 +589,7 @@ int ksg_schedule_batch(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint32
   HIPCHK(c, hipSetDevice(c->device));
   c->last_ms = 0.0;
   if (n == 0) return KSG_OK;
-  if (c->N == 0) {
+  if (c->cl.N == 0) {
     for (uint32_t i = 0; i < n; ++i) out_nodes[i] = KSG_OUT_NONODES;
     return KSG_OK;
   }
@@ -599,7 +599,7 @@ int ksg_schedule_batch(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint32
   int rc;
   if ((rc = batch_stage(c, run))) return rc;
   DivergeGuard guard{c};
-  if (c->dev.dbg & 16384) c->dbg_fail_next = true;  // KSG_DEBUG & 16384: fail the batch after its device work
+  if (c->cl.dev.dbg & 16384) c->dbg_fail_next = true;  // KSG_DEBUG & 16384: fail the batch after its device work
   guard.armed = true;  // device work from here on
   const ksg_pod_ext* dext = nullptr;
   if ((rc = batch_begin(c, run, rng_state, &dext))) return rc;
@@ -635,10 +635,10 @@ int ksg_schedule_batch_draws(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const 
   if (int rs_ = srv_stop(c)) return rs_;
   if (int rc = c->d_draws.grow(c, n)) return rc;
   HIPCHK(c, hipMemcpy(c->d_draws, draws, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
-  c->dev.draws = c->d_draws;  // (the generator state is now the index of the next value)
+  c->cl.dev.draws = c->d_draws;  // (the generator state is now the index of the next value)
   uint64_t state = 0;
   const int rc = ksg_schedule_batch(c, pods, n, ids, n_ids, &state, out_nodes);
-  c->dev.draws = nullptr;
+  c->cl.dev.draws = nullptr;
   if (rc == KSG_OK) *draws_used = (uint32_t)state;
   return rc;
 }

@@ -1,7 +1,10 @@
-// ksg_host.h — what the host translation units share: the context (struct ksg_ctx), the
-// owning scratch-buffer types, the error macros, the environment switches' parsers and the
-// helpers ksg_runtime.cpp defines and ksg_batch.cpp, ksg_without.cpp and ksg_preempt.cpp call, among them the
-// frame of the read-only batch queries (query_enter ... query_chunks).
+// ksg_host.h — what the host translation units share: the context (struct ksg_ctx) with the two
+// parts a node list determines (struct Cluster: the device tables and their geometry; struct
+// NodeMirror: the per-node half of the host mirror), the owning device-memory types (all
+// move-only), the error macros, the environment switches' parsers and the helpers
+// ksg_runtime.cpp defines and ksg_cluster.cpp, ksg_batch.cpp, ksg_without.cpp and
+// ksg_preempt.cpp call, among them the frame of the read-only batch queries (query_enter ...
+// query_chunks).
 #ifndef KSG_HOST_H_
 #define KSG_HOST_H_
 
@@ -16,6 +19,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -66,8 +70,16 @@ struct DevBuf {
   T* p = nullptr;
   size_t cap = 0;
   DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
+  // (move-only: the moved-from buffer is left empty)
+  DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      std::swap(p, o.p);
+      std::swap(cap, o.cap);
+    }
+    return *this;
+  }
   ~DevBuf() { release(); }
   operator T*() const { return p; }
   void release() {
@@ -110,6 +122,26 @@ struct HostBuf {
   }
 };
 
+// The fixed-size device arrays of one node list (dalloc adds them), freed with their owner.
+// Move-only; a moved-from owner holds none.
+struct DevAllocs {
+  std::vector<void*> v;
+  DevAllocs() = default;
+  DevAllocs(DevAllocs&& o) noexcept { v.swap(o.v); }
+  DevAllocs& operator=(DevAllocs&& o) noexcept {
+    if (this != &o) {
+      release();
+      v.swap(o.v);
+    }
+    return *this;
+  }
+  ~DevAllocs() { release(); }
+  void release() {
+    for (void* q : v) (void)hipFree(q);
+    v.clear();
+  }
+};
+
 struct PodRec {
   uint32_t host;
   int64_t cpu, mem;
@@ -130,6 +162,63 @@ constexpr size_t kFctlBytes = kFctlRuns + (size_t)2 * kFctlGroups * 8 * sizeof(u
 // stream time between the window kernels and evicts the node state the next
 // kernel reads from L2 (KSG_EVENT_FENCE=1 restores the default for A/B).
 inline const unsigned kTimingEvent = env_flag("KSG_EVENT_FENCE", false) ? hipEventDefault : hipEventDisableSystemFence;
+
+// Everything a node list determines: what build_cluster and node_ext_upload (ksg_cluster.cpp)
+// write, and nothing else. The context holds one (c->cl): ksg_set_cluster starts from an empty
+// one; ksg_update_cluster swaps the old one out, builds the new one beside it and swaps back on
+// any failure. It owns its device memory (allocs and the DevBufs); the pointers in dev, d_zmap
+// and d_lbl_* are views into allocs. Destroy one only while its device is current.
+struct Cluster {
+  uint32_t N = 0, nw = 0, n_pairs = 0, S = 0, D = 0;
+  uint32_t lo = 0, hi = 0, wlo = 0, nwords = 0, nwords_max = 0;
+  std::vector<uint32_t> shard_wlo_h;
+  int R = 1;
+  size_t lds = 0;
+  KsgDev dev{};
+  DevAllocs allocs;
+  DevBuf<uint32_t> d_shard_wlo;
+  DevBuf<int32_t> dbgbuf;  // dev.dbgbuf's owner (KSG_DEBUG & (8 | 32 | 64))
+  // scratch sized for the shard
+  DevBuf<uint8_t> d_fail;
+  DevBuf<int64_t> d_score;
+  DevBuf<uint8_t> d_rec_send, d_rec_recv;
+  uint32_t rec_bytes = 0;
+  DevBuf<int32_t> d_dpart, d_dglobal;
+  uint32_t dbg_corrupt = 0;         // KSG_DEBUG bits 22 / 23: corrupt the next COMMIT / BEGIN request's layout
+  bool win_d1 = true;               // phase A's single-commit drop bitmaps (KSG_WIN_D1=0: off; ksg_plain.hip)
+  uint64_t* d_zmap = nullptr;       // [D+1][nw] re-rank: nodes of each domain row
+  std::vector<int32_t> h_aff_pair;  // [affinity label][node] (ServiceAffinity, one rank)
+  int64_t max_cap = 0, min_cap = 0;
+  // calculateScore (priorities.go:27-37) stays in [0, 10] only while capacities lie in
+  // [0, 2^63 / 10] and requested totals are non-negative; score_bound() assumes that range.
+  // lr_wild: this node list, or a pod seen since ksg_set_cluster, can take a LeastRequested
+  // term out of it (a negative capacity or one whose x10 wraps, a negative request, a total
+  // that wraps): the int64 score kernels serve the context from then on (KsgDev.wide)
+  bool lr_wild = false;
+  unsigned __int128 static_mag = 0;  // max |score| of the terms ksg_set_static_terms added
+  // the node labels on the device (ksg_add_static_config evaluates more static terms from them)
+  const ksg_node* d_lbl_nodes = nullptr;
+  const uint32_t* d_lbl_pairs = nullptr;
+  const uint32_t* d_lbl_keys = nullptr;
+};
+static_assert(!std::is_copy_constructible<Cluster>::value && std::is_nothrow_move_constructible<Cluster>::value,
+              "Cluster is move-only");
+
+// The per-node half of the host mirror: what the committed pods add up to on each node and in
+// each service. As constructed: no pods on N nodes and S services.
+struct NodeMirror {
+  std::vector<int64_t> used_c, used_m;
+  std::vector<int64_t> sc_used;                    // [n_scalar][N] host mirror of scalar_used
+  std::unordered_map<uint64_t, uint32_t> key_ref;  // (key << 32) | node
+  std::vector<int32_t> svc_cnt;                    // S*N
+  std::vector<std::unordered_map<uint32_t, int32_t>> svc_ext;
+  std::vector<int32_t> svc_max, svc_total, svc_peer;
+  std::vector<std::map<uint64_t, uint32_t>> svc_members;  // seq -> host
+  NodeMirror() = default;
+  NodeMirror(uint32_t N, uint32_t S, uint32_t n_scalar)
+      : used_c(N, 0), used_m(N, 0), sc_used((size_t)n_scalar * N, 0), svc_cnt((size_t)S * N, 0), svc_ext(S),
+        svc_max(S, 0), svc_total(S, 0), svc_peer(S, -1), svc_members(S) {}
+};
 
 #pragma GCC visibility pop
 
@@ -163,24 +252,11 @@ struct ksg_ctx {
   // of its commits and the host mirror none, so every call fails until
   // ksg_set_cluster uploads the cluster again
   bool diverged = false;
-  uint32_t N = 0, nw = 0, n_pairs = 0, S = 0, D = 0;
-  uint32_t lo = 0, hi = 0, wlo = 0, nwords = 0, nwords_max = 0;
-  std::vector<uint32_t> shard_wlo_h;
-  int R = 1;
-  size_t lds = 0;
-  KsgDev dev{};
-  std::vector<void*> cluster_allocs;
-  DevBuf<uint32_t> d_shard_wlo;
-  DevBuf<int32_t> dbgbuf;  // dev.dbgbuf's owner (KSG_DEBUG & (8 | 32 | 64))
+  Cluster cl;  // the node list's parts
 
   // scratch
   DevBuf<ksg_pod> d_pods;
   DevBuf<uint32_t> d_ids;
-  DevBuf<uint8_t> d_fail;
-  DevBuf<int64_t> d_score;
-  DevBuf<uint8_t> d_rec_send, d_rec_recv;
-  uint32_t rec_bytes = 0;
-  DevBuf<int32_t> d_dpart, d_dglobal;
   DevBuf<int32_t> d_out;
   DevBuf<uint64_t> d_rng;
   DevBuf<int64_t> d_summary;
@@ -238,17 +314,11 @@ struct ksg_ctx {
   double last_update_us[3] = {0, 0, 0};
 
   // host mirror
-  std::vector<int64_t> used_c, used_m;
+  NodeMirror mir;
   // max over nodes of used_c / used_m for use_window: raised by each mirror add,
   // recomputed after anything else changes them (a removal, a negative total)
   int64_t mu_max = 0;
   bool mu_neg = false, mu_dirty = true;
-  std::unordered_map<uint64_t, uint32_t> key_ref;  // (key << 32) | node
-  std::vector<int32_t> svc_cnt;                    // S*N
-  std::vector<std::unordered_map<uint32_t, int32_t>> svc_ext;
-  std::vector<int32_t> svc_max, svc_total, svc_peer;
-  std::vector<int32_t> h_aff_pair;  // [affinity label][node] (ServiceAffinity, one rank; ksg_set_cluster)
-  std::vector<std::map<uint64_t, uint32_t>> svc_members;  // seq -> host
   std::unordered_map<uint64_t, PodRec> pods;
   uint64_t seq = 0;
 
@@ -266,7 +336,6 @@ struct ksg_ctx {
   DevBuf<uint8_t> d_t0img;   // the plain resolver's T0 images, one per window pod
   DevBuf<int32_t> d_dcnt;    // [W][D] per-pod anti-affinity domain counts (phase A pre-pass)
   DevBuf<int32_t> d_dmb;     // [W][D+1] re-rank: best score without the anti term per domain row
-  uint64_t* d_zmap = nullptr;  // [D+1][nw] re-rank: nodes of each domain row (cluster allocation)
   DevBuf<int32_t> d_etmax;    // [W] extension scores: TaintToleration max per window pod (count pass)
   DevBuf<int32_t> d_ethist;   // [W][KSG_TBINS] ... the histogram of its soft-taint counts
   DevBuf<uint64_t> d_epsoft;  // [W] ... the pods' untolerated soft taints as masks
@@ -278,8 +347,6 @@ struct ksg_ctx {
   double last_t0ms = 0;            // ... and between them: the exchange (sharded) and the T0 images
   double last_wsum = 0;            // window capacity W summed over the launches
   bool dbg_fail_next = false;      // KSG_DEBUG & 16384: the next window batch fails after its device work
-  uint32_t dbg_corrupt = 0;        // KSG_DEBUG bits 22 / 23: corrupt the next COMMIT / BEGIN request's layout
-  bool win_d1 = true;              // phase A's single-commit drop bitmaps (KSG_WIN_D1=0: off; ksg_plain.hip)
   // the fused window launch (KsgFused, ksg_plain.hip): one launch per window on one rank without
   // ServiceAntiAffinity or extensions (KSG_FUSED=0: phase A, T0 images and resolver apart)
   bool win_fused = true;
@@ -293,7 +360,6 @@ struct ksg_ctx {
   uint8_t* h_fctl = nullptr;        // pinned: the round's first slot and zeroed counters
   double last_hus[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // host us per phase of the last batch (ksg_last_batch_host_us)
   double totals[24] = {};  // ksg_batch_totals: the per-batch diagnostics summed over batches
-  int64_t max_cap = 0, min_cap = 0;
 
   // Commits of the last ksg_schedule_batch not yet replayed into the host
   // mirror: replayed while the next batch runs on the device, or before any
@@ -304,19 +370,12 @@ struct ksg_ctx {
   std::unordered_set<uint64_t> dfr_uids;
   int64_t dfr_sum = 0;   // sum of the deferred pods' requests (cpu + memory), capped
   bool dfr_neg = false;  // a deferred pod has a negative request
-  // calculateScore (priorities.go:27-37) stays in [0, 10] only while capacities lie in
-  // [0, 2^63 / 10] and requested totals are non-negative; score_bound() assumes that range.
-  // lr_wild: this node list, or a pod seen since ksg_set_cluster, can take a LeastRequested
-  // term out of it (a negative capacity or one whose x10 wraps, a negative request, a total
-  // that wraps): the int64 score kernels serve the context from then on (KsgDev.wide)
-  bool lr_wild = false;
   int64_t used_hi = 0;                // the largest committed total the mirror has held
   unsigned __int128 dfr_req = 0;      // requests of batches whose commits are not in the mirror yet
 
   // extensions (ksg_set_extensions; exact kernels, one rank, parity unpinned)
   bool ext_on = false;
   ksg_ext_config ext{};
-  std::vector<int64_t> sc_used;  // [n_scalar][N] host mirror of scalar_used
   std::unordered_map<uint64_t, std::array<int64_t, KSG_MAX_SCALAR>> ext_scalar;  // uid -> requests
   const ksg_pod_ext* cur_ext = nullptr;  // the _ext entry point's records for this call
   DevBuf<ksg_pod_ext> d_pext;            // device copy (batch / explain)
@@ -354,11 +413,6 @@ struct ksg_ctx {
   bool srv_stamps = false;      // KSG_SERVE_STAMPS=1: sum the server's per-stage cycles of each begin
   int64_t srv_grid_opts = -1;   // KSG_SERVE_GRID_OPTS (KsgSrvArgs.grid_opts; -1: by size)
   bool srv_debug = false;       // KSG_SERVE_DEBUG=1: the grid server's stage markers, reported on a fault
-  unsigned __int128 static_mag = 0;  // max |score| of the terms ksg_set_static_terms added
-  // the node labels on the device (ksg_add_static_config evaluates more static terms from them)
-  const ksg_node* d_lbl_nodes = nullptr;
-  const uint32_t* d_lbl_pairs = nullptr;
-  const uint32_t* d_lbl_keys = nullptr;
   bool srv_trace = false;       // KSG_SERVE_TRACE=1: every post, wait and relaunch to stderr
   double srv_stage[6] = {};     // (printed by ksg_destroy)
   uint64_t srv_stamped = 0;
@@ -408,6 +462,32 @@ int allgather(ksg_ctx* c, const void* dsend, void* drecv, size_t bytes);
 int allreduce_i32(ksg_ctx* c, Reduce op, const int32_t* dsend, int32_t* drecv, uint32_t n);
 bool anti_on(const ksg_ctx* c);
 uint8_t* rec_buf(ksg_ctx* c);
+// ... and the ones the node list (ksg_cluster.cpp) is built with
+int pick_R(uint32_t shard_nodes);
+void patch32(ksg_ctx* c, const void* addr, int32_t v);
+void patch64(ksg_ctx* c, const void* addr, int64_t v);
+void patch_or(ksg_ctx* c, const void* addr, uint64_t v);
+void patch_andnot(ksg_ctx* c, const void* addr, uint64_t v);
+void set_wide(ksg_ctx* c);
+void reset_mirror(ksg_ctx* c);
+// a zeroed device array of max(count, 1) elements, added to `owner` where one is given
+template <typename T>
+int dalloc(ksg_ctx* c, T** p, size_t count, std::vector<void*>* owner) {
+  void* q = nullptr;
+  HIPCHK(c, hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
+  HIPCHK(c, hipMemsetAsync(q, 0, std::max<size_t>(count, 1) * sizeof(T), c->st));
+  *p = static_cast<T*>(q);
+  if (owner) owner->push_back(q);
+  return KSG_OK;
+}
+// ... a fixed-size zeroed scratch buffer; the one it replaces is freed first
+template <typename T>
+int dalloc(ksg_ctx* c, DevBuf<T>& b, size_t count) {
+  b.release();
+  int rc = dalloc(c, &b.p, count, nullptr);
+  if (rc == KSG_OK) b.cap = std::max<size_t>(count, 1);
+  return rc;
+}
 
 // ---- the read-only batch queries' frame -------------------------------------------
 // ksg_explain_batch, ksg_prioritize_batch, ksg_headroom_batch (ksg_runtime.cpp),

@@ -32,7 +32,7 @@ int ksg_preempt_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, u
   if ((rc = query_validate(c, pods, ext, n, ids, n_ids, std::cref(position)))) return rc;
   WithoutTables tabs;
   if ((rc = without_tables(c, pods, n, absent_uids, n_absent, first_absent, false, true, &tabs))) return rc;
-  const uint32_t N = c->N;
+  const uint32_t N = c->cl.N;
   const ksg_pod_ext* dext;
   if ((rc = query_upload(c, pods, ext, n, ids, n_ids, false, &dext))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->d_wtab, c->h_wtab, tabs.bytes, hipMemcpyHostToDevice, c->st));
@@ -45,14 +45,14 @@ int ksg_preempt_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, u
   const size_t ob = o_vic + (size_t)n * max_victims * 4;
   if ((rc = c->d_vout.grow(c, ob)) || (rc = c->h_dn.grow(c, ob))) return rc;
   uint8_t* const vo = c->d_vout;
-  const size_t T = ksg_preempt_tiles(c->dev);
+  const size_t T = ksg_preempt_tiles(c->cl.dev);
   const size_t bpp = T * sizeof(KsgPreemptPart) + (node_victims ? (size_t)N * sizeof(uint32_t) : 0);
   const uint32_t per = query_per(c->preempt_stage, bpp, KSG_EXPLAIN_CHUNK, n);
   if ((rc = c->d_vpart.grow(c, (size_t)per * T * sizeof(KsgPreemptPart)))) return rc;
   if (node_victims && (rc = c->d_vnode.grow(c, (size_t)per * N))) return rc;
   const auto launch = [&](uint32_t a, uint32_t m) {
     w.first_absent = d_fa + a;  // (offset like the pods)
-    HIPCHK(c, ksg_launch_preempt(c->dev, w, tabs.ek, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m, max_victims,
+    HIPCHK(c, ksg_launch_preempt(c->cl.dev, w, tabs.ek, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m, max_victims,
                                  node_victims ? c->d_vnode.p : nullptr, reinterpret_cast<KsgPreemptPart*>(c->d_vpart.p),
                                  reinterpret_cast<int32_t*>(vo) + a, reinterpret_cast<uint32_t*>(vo + o_nv) + a,
                                  reinterpret_cast<uint32_t*>(vo + o_vic) + (size_t)a * max_victims,

@@ -1,9 +1,10 @@
 // ksg_runtime.cpp — host runtime of libkschedgpu.so: the C ABI in
 // include/kschedgpu.h except the batch entry points, the device-state mirror, the
 // RCCL exchange, the per-pod path (begin / commit / evaluate) with its resident
-// server, kubelet admission, the extensions, ksg_explain_batch and ksg_update_cluster. The batch driver
-// (ksg_schedule_batch and its variants) is ksg_batch.cpp; ksg_host.h holds what the
-// two files share (struct ksg_ctx, the scratch-buffer types, the helpers declared there).
+// server, kubelet admission, the pods' extension records and ksg_explain_batch. The batch driver
+// (ksg_schedule_batch and its variants) is ksg_batch.cpp, the node list (ksg_set_cluster,
+// ksg_update_cluster, the static terms, the node extensions) ksg_cluster.cpp; ksg_host.h holds
+// what the files share (struct ksg_ctx, the scratch-buffer types, the helpers declared there).
 //
 // Reference behaviour mirrored here:
 //   genericScheduler.Schedule / selectHost     pkg/scheduler/generic_scheduler.go:54-96
@@ -35,37 +36,12 @@ int fail(ksg_ctx* c, int code, const char* fmt, ...) {
   return code;
 }
 
-// File-local helpers, and the ones ksg_host.h declares for ksg_batch.cpp: none of them
+// File-local helpers, and the ones ksg_host.h declares for the other host files: none of them
 // is exported from the library.
 #pragma GCC visibility push(hidden)
 
-constexpr uint32_t kMaxNodesPerShard = KSG_R_MAX * KSG_NT;
 // ksg_explain_batch: device staging for the per-node codes of one chunk of pods
 constexpr size_t kExplainStageBytes = (size_t)64 << 20;
-
-template <typename T>
-int dalloc(ksg_ctx* c, T** p, size_t count, std::vector<void*>* owner) {
-  void* q = nullptr;
-  HIPCHK(c, hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-  HIPCHK(c, hipMemsetAsync(q, 0, std::max<size_t>(count, 1) * sizeof(T), c->st));
-  *p = static_cast<T*>(q);
-  if (owner) owner->push_back(q);
-  return KSG_OK;
-}
-// ... a fixed-size zeroed scratch buffer; the one it replaces is freed first
-template <typename T>
-int dalloc(ksg_ctx* c, DevBuf<T>& b, size_t count) {
-  b.release();
-  int rc = dalloc(c, &b.p, count, nullptr);
-  if (rc == KSG_OK) b.cap = std::max<size_t>(count, 1);
-  return rc;
-}
-
-void free_cluster(ksg_ctx* c) {
-  for (void* p : c->cluster_allocs) (void)hipFree(p);
-  c->cluster_allocs.clear();
-  c->have_cluster = false;
-}
 
 int pick_R(uint32_t shard_nodes) {
   const uint32_t r = (shard_nodes + KSG_NT - 1) / KSG_NT;
@@ -104,16 +80,16 @@ int flush_patches(ksg_ctx* c) {
 }
 
 int32_t peer_code(ksg_ctx* c, uint32_t s) {
-  if (c->svc_members[s].empty()) return -1;
-  const uint32_t h = c->svc_members[s].begin()->second;
-  return h < c->N ? (int32_t)h : -2;
+  if (c->mir.svc_members[s].empty()) return -1;
+  const uint32_t h = c->mir.svc_members[s].begin()->second;
+  return h < c->cl.N ? (int32_t)h : -2;
 }
 
 int32_t recompute_max(ksg_ctx* c, uint32_t s) {
   int32_t m = 0;
-  const int32_t* row = c->svc_cnt.data() + (size_t)s * c->N;
-  for (uint32_t n = 0; n < c->N; ++n) m = std::max(m, row[n]);
-  for (auto& kv : c->svc_ext[s]) m = std::max(m, kv.second);
+  const int32_t* row = c->mir.svc_cnt.data() + (size_t)s * c->cl.N;
+  for (uint32_t n = 0; n < c->cl.N; ++n) m = std::max(m, row[n]);
+  for (auto& kv : c->mir.svc_ext[s]) m = std::max(m, kv.second);
   return m;
 }
 
@@ -133,55 +109,55 @@ int mirror_add(ksg_ctx* c, uint32_t h, const ksg_pod* p, const uint32_t* ids, bo
     if (k >= c->cfg.max_conflict_keys)
       return fail(c, KSG_ERR_CAPACITY, "conflict key %u >= max_conflict_keys %u", k, c->cfg.max_conflict_keys);
   for (uint32_t s : r.svcs)
-    if (s >= c->S) return fail(c, KSG_ERR_ARG, "service %u >= n_services %u", s, c->S);
+    if (s >= c->cl.S) return fail(c, KSG_ERR_ARG, "service %u >= n_services %u", s, c->cl.S);
   for (uint32_t q = 0; q < KSG_MAX_SCALAR; ++q) r.scalar[q] = 0;
   if (c->ext_on && c->ext.n_scalar) {  // extension: the pod's extended resource requests
     auto it = c->ext_scalar.find(p->uid);
     if (it != c->ext_scalar.end())
       for (uint32_t q = 0; q < c->ext.n_scalar; ++q) r.scalar[q] = it->second[q];
-    if (h < c->N)
+    if (h < c->cl.N)
       for (uint32_t q = 0; q < c->ext.n_scalar; ++q) {
         if (!r.scalar[q]) continue;
-        int64_t& u = c->sc_used[(size_t)q * c->N + h];
+        int64_t& u = c->mir.sc_used[(size_t)q * c->cl.N + h];
         u = (int64_t)((uint64_t)u + (uint64_t)r.scalar[q]);
-        if (emit) patch64(c, c->dev.scalar_used + (size_t)q * c->N + h, u);
+        if (emit) patch64(c, c->cl.dev.scalar_used + (size_t)q * c->cl.N + h, u);
       }
   }
-  if (h < c->N) {
-    c->used_c[h] = (int64_t)((uint64_t)c->used_c[h] + (uint64_t)r.cpu);
-    c->used_m[h] = (int64_t)((uint64_t)c->used_m[h] + (uint64_t)r.mem);
-    c->used_hi = std::max(c->used_hi, std::max(c->used_c[h], c->used_m[h]));
-    if (c->mu_neg || c->used_c[h] < 0 || c->used_m[h] < 0) c->mu_dirty = true;
-    else c->mu_max = std::max(c->mu_max, std::max(c->used_c[h], c->used_m[h]));
+  if (h < c->cl.N) {
+    c->mir.used_c[h] = (int64_t)((uint64_t)c->mir.used_c[h] + (uint64_t)r.cpu);
+    c->mir.used_m[h] = (int64_t)((uint64_t)c->mir.used_m[h] + (uint64_t)r.mem);
+    c->used_hi = std::max(c->used_hi, std::max(c->mir.used_c[h], c->mir.used_m[h]));
+    if (c->mu_neg || c->mir.used_c[h] < 0 || c->mir.used_m[h] < 0) c->mu_dirty = true;
+    else c->mu_max = std::max(c->mu_max, std::max(c->mir.used_c[h], c->mir.used_m[h]));
     if (emit) {
-      patch64(c, c->dev.used_cpu + h, c->used_c[h]);
-      patch64(c, c->dev.used_mem + h, c->used_m[h]);
+      patch64(c, c->cl.dev.used_cpu + h, c->mir.used_c[h]);
+      patch64(c, c->cl.dev.used_mem + h, c->mir.used_m[h]);
     }
     for (uint32_t k : r.keys) {
-      const uint32_t ref = ++c->key_ref[((uint64_t)k << 32) | h];
-      if (ref == 1 && emit) patch_or(c, c->dev.keymap + (size_t)k * c->nw + (h >> 6), 1ULL << (h & 63));
+      const uint32_t ref = ++c->mir.key_ref[((uint64_t)k << 32) | h];
+      if (ref == 1 && emit) patch_or(c, c->cl.dev.keymap + (size_t)k * c->cl.nw + (h >> 6), 1ULL << (h & 63));
     }
   }
   for (uint32_t s : r.svcs) {
     int32_t v;
-    if (h < c->N) {
-      v = ++c->svc_cnt[(size_t)s * c->N + h];
-      if (emit) patch32(c, c->dev.svc_cnt + (size_t)s * c->N + h, v);
-      if (emit && v == 1) patch_or(c, c->dev.svc_bits + (size_t)s * c->nw + (h >> 6), 1ULL << (h & 63));
+    if (h < c->cl.N) {
+      v = ++c->mir.svc_cnt[(size_t)s * c->cl.N + h];
+      if (emit) patch32(c, c->cl.dev.svc_cnt + (size_t)s * c->cl.N + h, v);
+      if (emit && v == 1) patch_or(c, c->cl.dev.svc_bits + (size_t)s * c->cl.nw + (h >> 6), 1ULL << (h & 63));
     } else {
-      v = ++c->svc_ext[s][h];
+      v = ++c->mir.svc_ext[s][h];
     }
-    if (v > c->svc_max[s]) {
-      c->svc_max[s] = v;
-      if (emit) patch32(c, c->dev.svc_max + s, v);
+    if (v > c->mir.svc_max[s]) {
+      c->mir.svc_max[s] = v;
+      if (emit) patch32(c, c->cl.dev.svc_max + s, v);
     }
-    ++c->svc_total[s];
-    if (emit) patch32(c, c->dev.svc_total + s, c->svc_total[s]);
-    c->svc_members[s][r.seq] = h;
+    ++c->mir.svc_total[s];
+    if (emit) patch32(c, c->cl.dev.svc_total + s, c->mir.svc_total[s]);
+    c->mir.svc_members[s][r.seq] = h;
     const int32_t pc = peer_code(c, s);
-    if (pc != c->svc_peer[s]) {
-      c->svc_peer[s] = pc;
-      if (emit) patch32(c, c->dev.svc_peer + s, pc);
+    if (pc != c->mir.svc_peer[s]) {
+      c->mir.svc_peer[s] = pc;
+      if (emit) patch32(c, c->cl.dev.svc_peer + s, pc);
     }
   }
   c->pods.emplace(p->uid, std::move(r));
@@ -189,19 +165,10 @@ int mirror_add(ksg_ctx* c, uint32_t h, const ksg_pod* p, const uint32_t* ids, bo
 }
 
 void reset_mirror(ksg_ctx* c) {
-  c->used_c.assign(c->N, 0);
+  c->mir = NodeMirror(c->cl.N, c->cl.S, c->ext.n_scalar);
   c->mu_dirty = true;
   c->used_hi = 0;
-  c->used_m.assign(c->N, 0);
-  c->sc_used.assign((size_t)c->ext.n_scalar * c->N, 0);
   c->ext_scalar.clear();
-  c->key_ref.clear();
-  c->svc_cnt.assign((size_t)c->S * c->N, 0);
-  c->svc_ext.assign(c->S, {});
-  c->svc_max.assign(c->S, 0);
-  c->svc_total.assign(c->S, 0);
-  c->svc_peer.assign(c->S, -1);
-  c->svc_members.assign(c->S, {});
   c->pods.clear();
   c->seq = 0;
   c->patches.clear();
@@ -217,18 +184,18 @@ int check_pod(ksg_ctx* c, const ksg_pod* p, const uint32_t* ids, size_t n_ids) {
   if (!in(p->ports_off, p->n_ports) || !in(p->pds_off, p->n_pds) || !in(p->sel_off, p->n_sel) ||
       !in(p->svcs_off, p->n_svcs))
     return fail(c, KSG_ERR_ARG, "pod id list out of range");
-  if (p->host < -2 || p->host >= (int32_t)c->N) return fail(c, KSG_ERR_ARG, "pod host %d out of range", p->host);
-  if (p->service < -1 || p->service >= (int32_t)c->S) return fail(c, KSG_ERR_ARG, "pod service out of range");
+  if (p->host < -2 || p->host >= (int32_t)c->cl.N) return fail(c, KSG_ERR_ARG, "pod host %d out of range", p->host);
+  if (p->service < -1 || p->service >= (int32_t)c->cl.S) return fail(c, KSG_ERR_ARG, "pod service out of range");
   for (uint32_t i = 0; i < p->n_ports; ++i)
     if (ids[p->ports_off + i] >= c->cfg.max_conflict_keys) return fail(c, KSG_ERR_CAPACITY, "port key out of range");
   for (uint32_t i = 0; i < p->n_pds; ++i)
     if (ids[p->pds_off + i] >= c->cfg.max_conflict_keys) return fail(c, KSG_ERR_CAPACITY, "pd key out of range");
   for (uint32_t i = 0; i < p->n_sel; ++i)
-    if (ids[p->sel_off + i] >= c->n_pairs) return fail(c, KSG_ERR_ARG, "selector pair out of range");
+    if (ids[p->sel_off + i] >= c->cl.n_pairs) return fail(c, KSG_ERR_ARG, "selector pair out of range");
   for (uint32_t i = 0; i < p->n_svcs; ++i)
-    if (ids[p->svcs_off + i] >= c->S) return fail(c, KSG_ERR_ARG, "service id out of range");
+    if (ids[p->svcs_off + i] >= c->cl.S) return fail(c, KSG_ERR_ARG, "service id out of range");
   for (uint32_t j = 0; j < c->cfg.n_aff_labels; ++j)
-    if (p->aff_pair[j] >= (int32_t)c->n_pairs || p->aff_pair[j] < KSG_AFF_INVALID)
+    if (p->aff_pair[j] >= (int32_t)c->cl.n_pairs || p->aff_pair[j] < KSG_AFF_INVALID)
       return fail(c, KSG_ERR_ARG, "affinity pair out of range");
   return KSG_OK;
 }
@@ -300,9 +267,9 @@ size_t call_ids_extent(const ksg_ctx* c, const ksg_pod* p) {
 }
 
 // the shard records decide reads: all-gathered (exchange path) or this rank's own
-uint8_t* rec_buf(ksg_ctx* c) { return c->xchg ? c->d_rec_recv.p : c->d_rec_send.p; }
+uint8_t* rec_buf(ksg_ctx* c) { return c->xchg ? c->cl.d_rec_recv.p : c->cl.d_rec_send.p; }
 
-bool anti_on(const ksg_ctx* c) { return c->cfg.n_anti > 0 && c->dev.n_domains_total > 0; }
+bool anti_on(const ksg_ctx* c) { return c->cfg.n_anti > 0 && c->cl.dev.n_domains_total > 0; }
 
 // ---- cross-rank exchange: RCCL over xGMI, or the caller's host transport ----
 // recv[g * bytes, (g + 1) * bytes) = rank g's send, on c->st
@@ -360,21 +327,21 @@ int scan_exchange(ksg_ctx* c, const ksg_pod* dpod, const uint32_t* dids, int mod
   const bool anti = anti_on(c);
   const bool tt = dext != nullptr && c->ext.w_taint_toleration != 0;
   if ((anti || tt) && c->xchg) {
-    HIPCHK(c, ksg_launch_scan(c->R, anti, c->dev, dpod, dids, mode, 1, nullptr, nullptr, c->d_rec_send,
-                              c->d_dpart, nullptr, c->st, dext));
-    const uint32_t D = c->dev.n_domains_total;
-    int rc = anti ? allreduce_i32(c, Reduce::Sum, c->d_dpart, c->d_dglobal, D) : KSG_OK;
-    if (!rc && tt) rc = allreduce_i32(c, Reduce::Max, c->d_dpart + D, c->d_dglobal + D, 1);
+    HIPCHK(c, ksg_launch_scan(c->cl.R, anti, c->cl.dev, dpod, dids, mode, 1, nullptr, nullptr, c->cl.d_rec_send,
+                              c->cl.d_dpart, nullptr, c->st, dext));
+    const uint32_t D = c->cl.dev.n_domains_total;
+    int rc = anti ? allreduce_i32(c, Reduce::Sum, c->cl.d_dpart, c->cl.d_dglobal, D) : KSG_OK;
+    if (!rc && tt) rc = allreduce_i32(c, Reduce::Max, c->cl.d_dpart + D, c->cl.d_dglobal + D, 1);
     if (rc) return rc;
-    HIPCHK(c, ksg_launch_scan(c->R, anti, c->dev, dpod, dids, mode, 2, fail_out, score_out, c->d_rec_send,
-                              nullptr, c->d_dglobal, c->st, dext));
+    HIPCHK(c, ksg_launch_scan(c->cl.R, anti, c->cl.dev, dpod, dids, mode, 2, fail_out, score_out, c->cl.d_rec_send,
+                              nullptr, c->cl.d_dglobal, c->st, dext));
   } else {
-    HIPCHK(c, ksg_launch_scan(c->R, anti, c->dev, dpod, dids, mode, 0, fail_out, score_out, c->d_rec_send,
+    HIPCHK(c, ksg_launch_scan(c->cl.R, anti, c->cl.dev, dpod, dids, mode, 0, fail_out, score_out, c->cl.d_rec_send,
                               nullptr, nullptr, c->st, dext));
   }
   if (mode == KSG_MODE_BEGIN) {
     if (c->xchg) {
-      int rc = allgather(c, c->d_rec_send, c->d_rec_recv, c->rec_bytes);
+      int rc = allgather(c, c->cl.d_rec_send, c->cl.d_rec_recv, c->cl.rec_bytes);
       if (rc) return rc;
     }  // (one rank: decide reads the record where the scan wrote it, rec_buf)
   }
@@ -438,22 +405,22 @@ int wait_device(ksg_ctx* c) {
 // the grid server: plain configurations (no ServiceAntiAffinity, no extensions)
 // past srv_grid_min nodes, one scan workgroup per 256 nodes (<= 255)
 // nodes per thread of the grid server's scan workgroups
-uint32_t srv_npt(const ksg_ctx* c) { return c->hi - c->lo > c->srv_npt4_min ? 4u : 1u; }
+uint32_t srv_npt(const ksg_ctx* c) { return c->cl.hi - c->cl.lo > c->srv_npt4_min ? 4u : 1u; }
 
 bool srv_grid(const ksg_ctx* c) {
-  const uint32_t n = c->hi - c->lo, per = KSG_GSRV_NT * srv_npt(c);
+  const uint32_t n = c->cl.hi - c->cl.lo, per = KSG_GSRV_NT * srv_npt(c);
   // (extensions: the filters and BalancedAllocation are per node; TaintToleration normalises over
   // the filtered set: the scan workgroups exchange their maxima through device memory)
   // (ServiceAntiAffinity: the domain counts likewise, up to KSG_GSRV_MAXD domains, without extensions)
-  return c->srv_grid_on && !(anti_on(c) && (c->ext_on || c->dev.n_domains_total > KSG_GSRV_MAXD)) &&
+  return c->srv_grid_on && !(anti_on(c) && (c->ext_on || c->cl.dev.n_domains_total > KSG_GSRV_MAXD)) &&
          !(c->ext_on && !c->srv_grid_ext) &&
          n > c->srv_grid_min &&
          (n + per - 1) / per <= KSG_GSRV_MAXW;
 }
 
 bool srv_eligible(const ksg_ctx* c) {
-  return c->srv_enabled && c->world == 1 && !c->xchg && (c->R <= KSG_SRV_MAX_R || srv_grid(c)) && !c->dev.wide &&
-         c->N > 0;
+  return c->srv_enabled && c->world == 1 && !c->xchg && (c->cl.R <= KSG_SRV_MAX_R || srv_grid(c)) && !c->cl.dev.wide &&
+         c->cl.N > 0;
 }
 
 int srv_alloc(ksg_ctx* c) {
@@ -479,7 +446,7 @@ int srv_launch(ksg_ctx* c) {
   const uint32_t r0 = __atomic_load_n(&c->srv_box->resp[0], __ATOMIC_ACQUIRE);
   if ((int32_t)(r0 - c->srv_served) > 0) c->srv_served = r0;
   const uint32_t start_seq = c->srv_served;
-  const size_t nf = ((size_t)(c->hi - c->lo) + 3 & ~(size_t)3) + 64;  // (the grid server stores 4 codes at a time)
+  const size_t nf = ((size_t)(c->cl.hi - c->cl.lo) + 3 & ~(size_t)3) + 64;  // (the grid server stores 4 codes at a time)
   if (c->srv_fail_cap < nf) {
     if (c->srv_fail) (void)hipHostFree(c->srv_fail);
     c->srv_fail = nullptr;
@@ -494,7 +461,7 @@ int srv_launch(ksg_ctx* c) {
                (c->srv_stamps ? 1u : 0u) | (c->srv_debug ? 2u : 0u),
                nullptr, 0, ++c->srv_epoch, 0};
   if (srv_grid(c)) {
-    const uint32_t n = c->hi - c->lo;
+    const uint32_t n = c->cl.hi - c->cl.lo;
     const size_t need = sizeof(KsgSrvGrid);
     if (c->srv_grid_cap < need) {
       if (c->srv_grid) (void)hipFree(c->srv_grid);
@@ -510,9 +477,9 @@ int srv_launch(ksg_ctx* c) {
     // past 64 scan workgroups their polls of the host block crowd the link: each sleeps ~0.2 us
     // more between polls (measured: 50,000 nodes 73 -> 38 us per pod; no gain at 15,000)
     a.grid_opts = c->srv_grid_opts >= 0 ? (uint32_t)c->srv_grid_opts : a.n_workers > 64 ? 0x10u : 0u;
-    HIPCHK(c, ksg_launch_serve_grid((int)npt, c->ext_on, c->dev, a, c->st));
+    HIPCHK(c, ksg_launch_serve_grid((int)npt, c->ext_on, c->cl.dev, a, c->st));
   } else {
-    HIPCHK(c, ksg_launch_serve(c->R, anti_on(c), c->ext_on, c->dev, a, c->st));
+    HIPCHK(c, ksg_launch_serve(c->cl.R, anti_on(c), c->ext_on, c->cl.dev, a, c->st));
   }
   c->srv_running = true;
   ++c->srv_launches;
@@ -597,11 +564,11 @@ int srv_post(ksg_ctx* c, const uint32_t* hdr_in, uint32_t* seq_out) {
   uint32_t hdr[KSG_SRV_HDR_DW];
   memcpy(hdr, hdr_in, sizeof hdr);
   if (!ctl) hdr[KSG_SRVH_ARG] = c->srv_last_ctl;
-  if (c->dbg_corrupt) {
+  if (c->cl.dbg_corrupt) {
     const uint32_t bit = hdr[KSG_SRVH_KIND] == KSG_SRV_COMMIT ? 1u : hdr[KSG_SRVH_KIND] == KSG_SRV_BEGIN ? 2u : 0u;
-    if (c->dbg_corrupt & bit) {
+    if (c->cl.dbg_corrupt & bit) {
       hdr[KSG_SRVH_IDS_AT] = KSG_SRV_PAY_DW + 1;  // (past the payload: req_bad)
-      c->dbg_corrupt &= ~bit;
+      c->cl.dbg_corrupt &= ~bit;
     }
   }
   const uint32_t seq = ++c->srv_seq;
@@ -633,7 +600,7 @@ int srv_call(ksg_ctx* c, const uint32_t* hdr, uint32_t* resp4) {
 // A BEGIN on either server: {k | ~0u (no peer) | KSG_SRV_BADREQ, max} and the
 // tie words into srv_tw. The grid server's parts are merged here.
 int srv_begin(ksg_ctx* c, const uint32_t* hdr, uint32_t* resp4) {
-  const uint32_t n = c->hi - c->lo, nwd = (n + 63) / 64;
+  const uint32_t n = c->cl.hi - c->cl.lo, nwd = (n + 63) / 64;
   if (!srv_grid(c)) {
     if (int rc = srv_call(c, hdr, resp4)) return rc;
     if (resp4[1] != KSG_SRV_BADREQ && resp4[1] != ~0u && resp4[1] > 0)
@@ -711,16 +678,16 @@ int srv_stop(ksg_ctx* c) {
 // int32): once a |score| could reach KSG_SCORE_BOUND by the weights, or a LeastRequested
 // term can leave the [0, 10] that bound assumes
 void set_wide(ksg_ctx* c) {
-  c->dev.wide = score_bound(c->cfg, c->ext.w_taint_toleration, c->ext.w_balanced) + c->static_mag >=
+  c->cl.dev.wide = score_bound(c->cfg, c->ext.w_taint_toleration, c->ext.w_balanced) + c->cl.static_mag >=
                     (unsigned __int128)KSG_SCORE_BOUND ||
-                (c->lr_wild && c->cfg.w_least_requested != 0);
+                (c->cl.lr_wild && c->cfg.w_least_requested != 0);
 }
 
 // Pods about to be filtered, scored or committed. A negative request, or a requested total that could pass 2^63 - 1 and wrap
 // negative, takes calculateScore out of [0, 10]: the context turns to the int64 kernels
 // (the servers leave the stream and decline it from here on) until ksg_set_cluster.
 int note_requests(ksg_ctx* c, const ksg_pod* pods, uint32_t n) {
-  if (c->lr_wild || c->cfg.w_least_requested == 0) return KSG_OK;
+  if (c->cl.lr_wild || c->cfg.w_least_requested == 0) return KSG_OK;
   bool wild = c->used_hi < 0;
   unsigned __int128 sum = 0;
   for (uint32_t i = 0; i < n; ++i) {
@@ -730,8 +697,8 @@ int note_requests(ksg_ctx* c, const ksg_pod* pods, uint32_t n) {
   wild = wild || (unsigned __int128)(uint64_t)std::max<int64_t>(c->used_hi, 0) + c->dfr_req + sum >
                      (unsigned __int128)INT64_MAX;
   if (!wild) return KSG_OK;
-  c->lr_wild = true;
-  if (!c->dev.wide) {
+  c->cl.lr_wild = true;
+  if (!c->cl.dev.wide) {
     if (int rc = srv_stop(c)) return rc;
     set_wide(c);
   }
@@ -797,7 +764,7 @@ int query_enter(ksg_ctx* c, const ksg_pod_ext* ext, uint32_t n, const uint32_t* 
   HIPCHK(c, hipSetDevice(c->device));
   *last_ms = 0.0;
   if (n == 0) return kQueryDone;
-  if (c->N == 0) return KSG_NONODES;
+  if (c->cl.N == 0) return KSG_NONODES;
   if (n_ids && !ids) return fail(c, KSG_ERR_ARG, "ids missing");
   return KSG_OK;
 }
@@ -1011,9 +978,9 @@ int ksg_create_sharded(const ksg_config* cfg, int device, int rank, int world, c
 
 int ksg_destroy(ksg_ctx* c) {
   if (!c) return KSG_OK;
-  if (c->dev.dbgbuf) {  // debug stamps (KSG_DEBUG & 8): cycles/64 per resolver section
+  if (c->cl.dev.dbgbuf) {  // debug stamps (KSG_DEBUG & 8): cycles/64 per resolver section
     int32_t h[32];
-    (void)hipMemcpy(h, c->dev.dbgbuf, sizeof h, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(h, c->cl.dev.dbgbuf, sizeof h, hipMemcpyDeviceToHost);
     fprintf(stderr, "ksg stamps (x64 cycles, committer wave): ring-wait %d head %d recheck-last-slot %d "
             "wait-checkers %d select %d commit %d | drop-path pods %d unpredicted commits %d\n",
             h[0], h[1], h[2], h[3], h[4], h[5], h[7], h[8]);
@@ -1042,7 +1009,6 @@ int ksg_destroy(ksg_ctx* c) {
   }
   (void)hipSetDevice(c->device);
   if (c->st) (void)hipStreamSynchronize(c->st);
-  free_cluster(c);
   if (c->comm) ncclCommDestroy(c->comm);
   if (c->h_run) (void)hipHostFree(c->h_run);
   if (c->h_fctl) (void)hipHostFree(c->h_fctl);
@@ -1059,412 +1025,20 @@ int ksg_destroy(ksg_ctx* c) {
   for (auto& e : c->wev)
     if (e) (void)hipEventDestroy(e);
   if (c->st) (void)hipStreamDestroy(c->st);
-  delete c;  // (the scratch buffers free themselves: the device is set and the stream was synchronised above)
+  // (the node list's parts, c->cl, and the scratch buffers free themselves: the device is set and
+  // the stream was synchronised above)
+  delete c;
   return KSG_OK;
 }
 
 const char* ksg_last_error(ksg_ctx* c) { return c ? c->err.c_str() : "null context"; }
-
-// ksg_set_cluster's and ksg_update_cluster's checks of the node arrays (n_pairs >= 1)
-static int check_nodes(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const uint32_t* node_pairs,
-                       uint32_t n_node_pairs, uint32_t n_pairs) {
-  if (n_nodes && !nodes) return fail(c, KSG_ERR_ARG, "nodes == NULL");
-  for (uint32_t i = 0; i < n_nodes; ++i) {
-    if ((size_t)nodes[i].label_off + nodes[i].n_labels > n_node_pairs)
-      return fail(c, KSG_ERR_ARG, "node %u label range out of bounds", i);
-    for (uint32_t k = 0; k < nodes[i].n_labels; ++k)
-      if (node_pairs[nodes[i].label_off + k] >= n_pairs || node_pairs[nodes[i].label_off + k] == 0)
-        return fail(c, KSG_ERR_ARG, "node %u has invalid pair id", i);
-  }
-  return KSG_OK;
-}
-
-// Everything a node list determines, built into the context in fresh allocations: the shard
-// geometry, the static tables, zeroed pod-state arrays (svc_peer -1), the scratch sized for the
-// shard. The caller has put the previous list's parts away (free_cluster, or ClusterParts for
-// ksg_update_cluster); the host mirror is not touched.
-static int build_cluster(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const uint32_t* node_pairs,
-                         uint32_t n_node_pairs, const uint32_t* pair_keys, uint32_t n_pairs, uint32_t n_services) {
-  c->N = n_nodes;
-  c->nw = (n_nodes + 63) / 64;
-  c->n_pairs = n_pairs;
-  c->S = n_services;
-  // shard by 64-node words
-  c->shard_wlo_h.resize(c->world);
-  c->nwords_max = 0;
-  uint32_t max_shard_nodes = 0;
-  for (int g = 0; g < c->world; ++g) {
-    uint32_t a, b;
-    ksg_shard_words(c->nw, (uint32_t)g, (uint32_t)c->world, &a, &b);
-    c->shard_wlo_h[g] = a;
-    c->nwords_max = std::max(c->nwords_max, b - a);
-    max_shard_nodes = std::max(max_shard_nodes, std::min(b * 64, n_nodes) - std::min(a * 64, n_nodes));
-    if (g == c->rank) {
-      c->wlo = a;
-      c->nwords = b - a;
-      c->lo = std::min(a * 64, n_nodes);
-      c->hi = std::min(b * 64, n_nodes);
-    }
-  }
-  if (max_shard_nodes > kMaxNodesPerShard)
-    return fail(c, KSG_ERR_CAPACITY, "shard of %u nodes exceeds %u (use more GPUs)", max_shard_nodes,
-                kMaxNodesPerShard);
-  c->R = pick_R(std::max<uint32_t>(max_shard_nodes, 1));
-
-  // anti-affinity domains: dense index of each pair whose key is the label
-  std::vector<int32_t> dom_of_pair((size_t)std::max<uint32_t>(c->cfg.n_anti, 1) * n_pairs, -1);
-  c->D = 0;
-  KsgDev& d = c->dev;
-  d = KsgDev{};
-  for (uint32_t a = 0; a < c->cfg.n_anti; ++a) {
-    d.anti_dom_off[a] = c->D;
-    uint32_t nd = 0;
-    for (uint32_t p = 1; p < n_pairs; ++p)
-      if ((pair_keys[p] & ~KSG_PAIR_INVALID) == c->cfg.anti_key[a]) dom_of_pair[(size_t)a * n_pairs + p] = (int32_t)nd++;
-    c->D += nd;
-  }
-  if (c->D > c->cfg.max_domains)
-    return fail(c, KSG_ERR_CAPACITY, "%u anti-affinity domains > max_domains %u", c->D, c->cfg.max_domains);
-  c->lds = (size_t)c->D * sizeof(int32_t);
-
-  auto* owner = &c->cluster_allocs;
-  int rc;
-  int64_t *cap_c, *cap_m;
-  double *inv_c, *inv_m;
-  uint64_t *sfit, *keymap, *pairmap;
-  int64_t* sscore;
-  int32_t *anti_dom, *aff_pair;
-  int64_t* gscore = nullptr;  // (int32 or int64 scores: sized for int64)
-  const size_t NN = std::max<uint32_t>(n_nodes, 1);
-  if ((rc = dalloc(c, &cap_c, NN, owner)) || (rc = dalloc(c, &cap_m, NN, owner)) ||
-      (rc = dalloc(c, &inv_c, NN, owner)) || (rc = dalloc(c, &inv_m, NN, owner)) ||
-      (rc = dalloc(c, &d.used_cpu, NN, owner)) || (rc = dalloc(c, &d.used_mem, NN, owner)) ||
-      (rc = dalloc(c, &sfit, std::max<uint32_t>(c->nw, 1), owner)) ||
-      (rc = dalloc(c, &sscore, NN, owner)) ||
-      (rc = dalloc(c, &keymap, (size_t)c->cfg.max_conflict_keys * std::max<uint32_t>(c->nw, 1), owner)) ||
-      (rc = dalloc(c, &pairmap, (size_t)n_pairs * std::max<uint32_t>(c->nw, 1), owner)) ||
-      (rc = dalloc(c, &d.svc_cnt, (size_t)std::max<uint32_t>(n_services, 1) * NN, owner)) ||
-      (rc = dalloc(c, &d.svc_bits, (size_t)std::max<uint32_t>(n_services, 1) * std::max<uint32_t>(c->nw, 1), owner)) ||
-      (rc = dalloc(c, &d.svc_max, std::max<uint32_t>(n_services, 1), owner)) ||
-      (rc = dalloc(c, &d.svc_total, std::max<uint32_t>(n_services, 1), owner)) ||
-      (rc = dalloc(c, &d.svc_peer, std::max<uint32_t>(n_services, 1), owner)) ||
-      (rc = dalloc(c, &anti_dom, (size_t)std::max<uint32_t>(c->cfg.n_anti, 1) * NN, owner)) ||
-      (rc = dalloc(c, &aff_pair, (size_t)std::max<uint32_t>(c->cfg.n_aff_labels, 1) * NN, owner)) ||
-      (c->R > KSG_R_LDS / 2 && (rc = dalloc(c, &gscore, (size_t)c->R * KSG_NT, owner))))
-    return rc;
-  if (n_services) HIPCHK(c, hipMemsetAsync(d.svc_peer, 0xff, n_services * sizeof(int32_t), c->st));
-
-  // upload nodes + static tables
-  std::vector<int64_t> hc(NN, 0), hm(NN, 0);
-  c->max_cap = 0;
-  c->min_cap = 0;
-  for (uint32_t i = 0; i < n_nodes; ++i) {
-    hc[i] = nodes[i].cap_milli_cpu;
-    hm[i] = nodes[i].cap_memory;
-    c->max_cap = std::max<int64_t>(c->max_cap, std::max<int64_t>(std::llabs(hc[i]), std::llabs(hm[i])));
-    c->min_cap = std::min<int64_t>(c->min_cap, std::min<int64_t>(hc[i], hm[i]));
-  }
-  HIPCHK(c, hipMemcpyAsync(cap_c, hc.data(), NN * 8, hipMemcpyHostToDevice, c->st));
-  HIPCHK(c, hipMemcpyAsync(cap_m, hm.data(), NN * 8, hipMemcpyHostToDevice, c->st));
-  // correctly rounded on host and device alike (lr_inv10, ksg_device.h)
-  std::vector<double> ic(NN, 0.0), im(NN, 0.0);
-  for (uint32_t i = 0; i < n_nodes; ++i) {
-    ic[i] = hc[i] > 0 ? 10.0 / (double)hc[i] : 0.0;
-    im[i] = hm[i] > 0 ? 10.0 / (double)hm[i] : 0.0;
-  }
-  HIPCHK(c, hipMemcpyAsync(inv_c, ic.data(), NN * 8, hipMemcpyHostToDevice, c->st));
-  HIPCHK(c, hipMemcpyAsync(inv_m, im.data(), NN * 8, hipMemcpyHostToDevice, c->st));
-  ksg_node* dn = nullptr;
-  uint32_t *dnp = nullptr, *dpk = nullptr;
-  int32_t* ddom = nullptr;
-  std::vector<void*> tmp;
-  // (the node labels stay with the cluster: ksg_add_static_config reads them)
-  if ((rc = dalloc(c, &dn, NN, owner)) || (rc = dalloc(c, &dnp, std::max<uint32_t>(n_node_pairs, 1), owner)) ||
-      (rc = dalloc(c, &dpk, n_pairs, owner)) || (rc = dalloc(c, &ddom, dom_of_pair.size(), &tmp)))
-    return rc;
-  c->d_lbl_nodes = dn;
-  c->d_lbl_pairs = dnp;
-  c->d_lbl_keys = dpk;
-  if (n_nodes) HIPCHK(c, hipMemcpyAsync(dn, nodes, n_nodes * sizeof(ksg_node), hipMemcpyHostToDevice, c->st));
-  if (n_node_pairs)
-    HIPCHK(c, hipMemcpyAsync(dnp, node_pairs, n_node_pairs * 4, hipMemcpyHostToDevice, c->st));
-  std::vector<uint32_t> pk(n_pairs, 0xffffffffu);
-  if (pair_keys)
-    for (uint32_t p = 1; p < n_pairs; ++p) pk[p] = pair_keys[p];
-  HIPCHK(c, hipMemcpyAsync(dpk, pk.data(), n_pairs * 4, hipMemcpyHostToDevice, c->st));
-  HIPCHK(c, hipMemcpyAsync(ddom, dom_of_pair.data(), dom_of_pair.size() * 4, hipMemcpyHostToDevice, c->st));
-  KsgStaticCfg sc{};
-  sc.n_presence = c->cfg.n_presence;
-  memcpy(sc.presence_n_keys, c->cfg.presence_n_keys, sizeof sc.presence_n_keys);
-  memcpy(sc.presence_keys, c->cfg.presence_keys, sizeof sc.presence_keys);
-  memcpy(sc.presence_flag, c->cfg.presence_flag, sizeof sc.presence_flag);
-  sc.n_pref = c->cfg.n_label_pref;
-  memcpy(sc.pref_key, c->cfg.pref_key, sizeof sc.pref_key);
-  memcpy(sc.pref_presence, c->cfg.pref_presence, sizeof sc.pref_presence);
-  memcpy(sc.w_pref, c->cfg.w_pref, sizeof sc.w_pref);
-  sc.w_equal = c->cfg.w_equal;
-  sc.n_anti = c->cfg.n_anti;
-  memcpy(sc.anti_key, c->cfg.anti_key, sizeof sc.anti_key);
-  sc.n_aff = c->cfg.n_aff_labels;
-  memcpy(sc.aff_key, c->cfg.aff_key, sizeof sc.aff_key);
-  HIPCHK(c, ksg_launch_static(sc, n_nodes, dn, dnp, dpk, ddom, n_pairs, c->nw, sfit, sscore, anti_dom, aff_pair,
-                              (unsigned long long*)pairmap, c->st));
-  // (ServiceAffinity: a host copy of each node's pair per affinity label, so the drop-in server's
-  // BEGIN carries a pod's requirements already resolved from its service's first peer)
-  c->h_aff_pair.clear();
-  if ((c->cfg.predicates & KSG_PRED_SERVICEAFFINITY) && c->cfg.n_aff_labels > 0 && c->world == 1) {
-    c->h_aff_pair.resize((size_t)c->cfg.n_aff_labels * NN);
-    HIPCHK(c, hipMemcpyAsync(c->h_aff_pair.data(), aff_pair, c->h_aff_pair.size() * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, c->st));
-    HIPCHK(c, hipStreamSynchronize(c->st));
-  }
-  // ServiceAntiAffinity re-rank (one anti priority, one rank, few domains, an
-  // LDS count per service): the nodes of each domain row, row D = unlabelled
-  c->d_zmap = nullptr;
-  uint32_t rr_dz = 0;
-  if (c->cfg.n_anti == 1 && c->cfg.w_anti[0] != 0 && c->D > 0 && c->D + 1 <= KSG_RR_MAXZ && c->world == 1 &&
-      n_services <= KSG_RR_MAXSVC && !(env_int("KSG_DEBUG", 0, INT32_MIN, INT32_MAX) & 2048)) {
-    rr_dz = c->D + 1;
-    if ((rc = dalloc(c, &c->d_zmap, (size_t)rr_dz * std::max<uint32_t>(c->nw, 1), owner))) return rc;
-    HIPCHK(c, ksg_launch_zonemap(n_nodes, anti_dom, c->D, c->nw, c->d_zmap, c->st));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->st));
-  for (void* p : tmp) (void)hipFree(p);
-
-  d.n_nodes = n_nodes;
-  d.nw = c->nw;
-  d.lo = c->lo;
-  d.hi = c->hi;
-  d.wlo = c->wlo;
-  d.nwords = c->nwords;
-  d.n_pairs = n_pairs;
-  d.n_services = n_services;
-  d.max_keys = c->cfg.max_conflict_keys;
-  d.n_domains_total = c->D;
-  d.rr_dz = rr_dz;
-  d.preds = c->cfg.predicates;
-  d.n_aff = (c->cfg.predicates & KSG_PRED_SERVICEAFFINITY) ? c->cfg.n_aff_labels : 0;
-  // ServiceAffinity predicates (label groups); none given: one over every label
-  d.n_aff_groups = c->cfg.n_aff_groups;
-  for (uint32_t g = 0; g < d.n_aff_groups; ++g) d.aff_group_mask[g] = c->cfg.aff_group_mask[g];
-  if (d.n_aff_groups == 0 && d.n_aff > 0) {
-    d.n_aff_groups = 1;
-    d.aff_group_mask[0] = (1u << d.n_aff) - 1u;
-  }
-  // (extension priorities count as priority configs)
-  const bool ext_prio = c->ext_on && (c->ext.w_taint_toleration || c->ext.w_balanced);
-  d.equal_fallback = c->cfg.n_priority_configs == 0 && !ext_prio;
-  // prioritizeNodes skips weight-0 configs; if every config has weight 0 the
-  // HostPriorityList is empty and Schedule returns *FitError.
-  bool any_weight = c->cfg.w_least_requested || c->cfg.w_service_spreading || c->cfg.w_equal || ext_prio;
-  for (uint32_t a = 0; a < c->cfg.n_anti; ++a) any_weight |= c->cfg.w_anti[a] != 0;
-  for (uint32_t q = 0; q < c->cfg.n_label_pref; ++q) any_weight |= c->cfg.w_pref[q] != 0;
-  d.empty_priorities = (!d.equal_fallback && !any_weight) ? 1 : 0;
-  c->static_mag = 0;  // (ksg_set_static_terms' terms end with the node list they were built for)
-  // int64 combined scores (exact kernels) once a |score| could reach KSG_SCORE_BOUND, or with a
-  // capacity whose LeastRequested term leaves [0, 10]: negative, or past 2^63 / 10 (the x10 wraps)
-  c->lr_wild = c->min_cap < 0 || c->max_cap > INT64_MAX / 10;
-  set_wide(c);
-  d.w_lr = c->cfg.w_least_requested;
-  d.w_spread = c->cfg.w_service_spreading;
-  d.n_anti = 0;
-  for (uint32_t a = 0; a < c->cfg.n_anti; ++a) {
-    d.w_anti[a] = c->cfg.w_anti[a];
-    if (c->cfg.w_anti[a]) d.n_anti = a + 1;
-  }
-  if (d.n_anti == 0) d.n_domains_total = 0;
-  bool any_pref = false;
-  for (uint32_t q = 0; q < c->cfg.n_label_pref; ++q) any_pref |= c->cfg.w_pref[q] != 0;
-  d.has_static_score = (c->cfg.w_equal != 0 || any_pref) ? 1 : 0;
-  d.dbg = (int)env_int("KSG_DEBUG", 0, INT32_MIN, INT32_MAX);
-  // KSG_DEBUG bit 22 / 23: the next COMMIT / BEGIN posted to the resident server carries an
-  // out-of-range payload layout (tests/test_gpu_serve.py: the server must reject it, not fault)
-  c->dbg_corrupt = ((uint32_t)d.dbg >> 22) & 3u;
-  c->win_d1 = env_flag("KSG_WIN_D1", true);
-  if (d.dbg & (8 | 32 | 64)) {  // (32: the plain resolver's inconsistency record, ksg_plain.hip; 64: phase-A stamps)
-    c->dbgbuf.release();  // (the previous node list's)
-    (void)hipMalloc((void**)&c->dbgbuf.p, KSG_DEBUG_COUNTER_WORDS * sizeof(int32_t));
-    (void)hipMemset(c->dbgbuf.p, 0, KSG_DEBUG_COUNTER_WORDS * sizeof(int32_t));
-    d.dbgbuf = c->dbgbuf.p;
-  }
-  d.has_static_fit = ((c->cfg.predicates & KSG_PRED_LABELSPRESENCE) && c->cfg.n_presence > 0) ? 1 : 0;
-  d.cap_cpu = cap_c;
-  d.cap_mem = cap_m;
-  d.inv10_cpu = inv_c;
-  d.inv10_mem = inv_m;
-  d.static_fit = sfit;
-  d.static_score = sscore;
-  d.keymap = keymap;
-  d.pairmap = pairmap;
-  d.anti_domain = anti_dom;
-  d.aff_pair = aff_pair;
-  d.score_scratch = gscore;
-  if (c->ext_on) {  // extensions: extended resources (allocatable, requested) and taint bitmaps
-    int64_t *scap = nullptr, *sused = nullptr;
-    uint64_t* tmap = nullptr;
-    const size_t nsr = std::max<uint32_t>(c->ext.n_scalar, 1);
-    if ((rc = dalloc(c, &scap, nsr * NN, owner)) || (rc = dalloc(c, &sused, nsr * NN, owner)) ||
-        (rc = dalloc(c, &tmap, (size_t)std::max<uint32_t>(c->ext.max_taints, 1) * std::max<uint32_t>(c->nw, 1), owner)))
-      return rc;
-    d.ext_filters = c->ext.filters;
-    d.w_taint = c->ext.w_taint_toleration;
-    d.w_bal = c->ext.w_balanced;
-    d.n_scalar = c->ext.n_scalar;
-    d.scalar_cap = scap;
-    d.scalar_used = sused;
-    d.taintmap = tmap;
-    d.ntaint = nullptr;
-    if (c->ext.max_taints <= 64) {  // (the window path's TaintToleration term: one mask per node)
-      uint64_t* ntm = nullptr;
-      if ((rc = dalloc(c, &ntm, NN, owner))) return rc;
-      d.ntaint = ntm;
-    }
-  }
-  c->lds = (size_t)d.n_domains_total * sizeof(int32_t);
-
-  // scratch sized for the shard
-  c->rec_bytes = (uint32_t)(sizeof(KsgRecordHdr) + (size_t)std::max<uint32_t>(c->nwords_max, 1) * 8);
-  if ((rc = dalloc(c, c->d_rec_send, c->rec_bytes)) ||
-      (rc = dalloc(c, c->d_rec_recv, (size_t)c->rec_bytes * c->world)) ||
-      (rc = dalloc(c, c->d_fail, NN)) || (rc = dalloc(c, c->d_score, NN)) ||
-      (rc = dalloc(c, c->d_dpart, (size_t)c->dev.n_domains_total + 1)) ||  // (+ the TaintToleration max)
-      (rc = dalloc(c, c->d_dglobal, (size_t)c->dev.n_domains_total + 1)) ||
-      (rc = dalloc(c, c->d_shard_wlo, c->world)))
-    return rc;
-  HIPCHK(c, hipMemcpyAsync(c->d_shard_wlo, c->shard_wlo_h.data(), c->world * 4, hipMemcpyHostToDevice, c->st));
-  HIPCHK(c, hipStreamSynchronize(c->st));
-  return KSG_OK;
-}
-
-int ksg_set_cluster(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const uint32_t* node_pairs,
-                    uint32_t n_node_pairs, const uint32_t* pair_keys, uint32_t n_pairs, uint32_t n_services) {
-  if (!c) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->st));
-  if (n_pairs == 0) n_pairs = 1;  // pair 0 always exists (empty)
-  if (int rc = check_nodes(c, nodes, n_nodes, node_pairs, n_node_pairs, n_pairs)) return rc;
-  free_cluster(c);
-  drop_deferred(c);
-  c->diverged = false;
-  c->ppw_est = 0.0;
-  if (int rc = build_cluster(c, nodes, n_nodes, node_pairs, n_node_pairs, pair_keys, n_pairs, n_services)) return rc;
-  reset_mirror(c);
-  c->have_cluster = true;
-  return KSG_OK;
-}
-
-int ksg_set_static_terms(ksg_ctx* c, const uint64_t* fit_words, const int64_t* score, int score_weighted) {
-  if (!c || (!fit_words && !score)) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (int rs = cluster_ok(c)) return rs;
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
-  // (a node failing the extra fit words reports KSG_FAIL_LABELSPRESENCE: the config must name it)
-  if (fit_words && !(c->cfg.predicates & KSG_PRED_LABELSPRESENCE))
-    return fail(c, KSG_ERR_ARG, "ksg_set_static_terms: fit words need KSG_PRED_LABELSPRESENCE in the config");
-  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
-  HIPCHK(c, hipSetDevice(c->device));
-  const uint32_t N = c->N, nw = (N + 63) / 64;
-  if (N == 0) return KSG_OK;
-  // a combined score stays int32 on the fast paths only while every |score| < 2^30
-  unsigned __int128 mag = 0;
-  if (score)
-    for (uint32_t n = 0; n < N; ++n) {
-      const unsigned __int128 m = score[n] < 0 ? (unsigned __int128)(0 - (uint64_t)score[n]) : (unsigned __int128)score[n];
-      mag = std::max(mag, m);
-    }
-  uint8_t* tmp = nullptr;
-  const size_t fb = fit_words ? (size_t)nw * 8 : 0, sb = score ? (size_t)N * 8 : 0;
-  HIPCHK(c, hipMalloc((void**)&tmp, fb + sb));
-  if (fit_words) HIPCHK(c, hipMemcpyAsync(tmp, fit_words, fb, hipMemcpyHostToDevice, c->st));
-  if (score) HIPCHK(c, hipMemcpyAsync(tmp + fb, score, sb, hipMemcpyHostToDevice, c->st));
-  KsgDev& d = c->dev;
-  HIPCHK(c, ksg_launch_static_fold(const_cast<uint64_t*>(d.static_fit), const_cast<int64_t*>(d.static_score),
-                                   fit_words ? reinterpret_cast<const uint64_t*>(tmp) : nullptr,
-                                   score ? reinterpret_cast<const int64_t*>(tmp + fb) : nullptr, nw, N,
-                                   d.has_static_fit, d.has_static_score, c->st));
-  HIPCHK(c, hipStreamSynchronize(c->st));
-  (void)hipFree(tmp);
-  if (fit_words) d.has_static_fit = 1;
-  if (score) {
-    d.has_static_score = 1;
-    c->static_mag += mag;
-    if (score_weighted) d.empty_priorities = 0;
-  }
-  set_wide(c);
-  return KSG_OK;
-}
-
-int ksg_add_static_config(ksg_ctx* c, const ksg_config* extra) {
-  if (!c || !extra) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (int rs = cluster_ok(c)) return rs;
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
-  if (extra->n_presence > KSG_MAX_PRESENCE || extra->n_label_pref > KSG_MAX_LABEL_PREF)
-    return fail(c, KSG_ERR_ARG, "ksg_add_static_config: more terms than the config's slots");
-  for (uint32_t q = 0; q < extra->n_presence; ++q)
-    if (extra->presence_n_keys[q] > KSG_MAX_PRESENCE_KEYS)
-      return fail(c, KSG_ERR_ARG, "ksg_add_static_config: presence predicate %u has too many keys", q);
-  // (a node failing the extra predicates reports KSG_FAIL_LABELSPRESENCE: the config must name it)
-  if (extra->n_presence && !(c->cfg.predicates & KSG_PRED_LABELSPRESENCE))
-    return fail(c, KSG_ERR_ARG, "ksg_add_static_config: LabelsPresence terms need KSG_PRED_LABELSPRESENCE in the config");
-  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
-  HIPCHK(c, hipSetDevice(c->device));
-  const uint32_t N = c->N, nw = (N + 63) / 64;
-  if (N == 0 || (extra->n_presence == 0 && extra->n_label_pref == 0)) return KSG_OK;
-  KsgStaticCfg sc{};  // (the terms only: no EqualPriority, anti-affinity domains or affinity pairs)
-  sc.n_presence = extra->n_presence;
-  memcpy(sc.presence_n_keys, extra->presence_n_keys, sizeof sc.presence_n_keys);
-  memcpy(sc.presence_keys, extra->presence_keys, sizeof sc.presence_keys);
-  memcpy(sc.presence_flag, extra->presence_flag, sizeof sc.presence_flag);
-  sc.n_pref = extra->n_label_pref;
-  memcpy(sc.pref_key, extra->pref_key, sizeof sc.pref_key);
-  memcpy(sc.pref_presence, extra->pref_presence, sizeof sc.pref_presence);
-  memcpy(sc.w_pref, extra->w_pref, sizeof sc.w_pref);
-  // |the pass's score| <= 10 x sum |w| (Go-int weights: a wrapped sum is still bounded by it)
-  unsigned __int128 mag = 0;
-  bool weighted = false;
-  for (uint32_t q = 0; q < extra->n_label_pref; ++q) {
-    const int64_t w = extra->w_pref[q];
-    mag += (unsigned __int128)(w < 0 ? 0 - (uint64_t)w : (uint64_t)w) * 10u;
-    weighted |= w != 0;
-  }
-  const bool do_fit = extra->n_presence > 0, do_score = extra->n_label_pref > 0;
-  const size_t fb = (size_t)nw * 8;
-  // the scratch pair, freed on every path out (an error return included)
-  struct Scratch {
-    uint8_t* p = nullptr;
-    ~Scratch() {
-      if (p) (void)hipFree(p);
-    }
-  } tmp;
-  HIPCHK(c, hipMalloc((void**)&tmp.p, fb + (size_t)N * 8));
-  uint64_t* xfit = reinterpret_cast<uint64_t*>(tmp.p);
-  int64_t* xscore = reinterpret_cast<int64_t*>(tmp.p + fb);
-  KsgDev& d = c->dev;
-  HIPCHK(c, ksg_launch_static_terms(sc, N, c->d_lbl_nodes, c->d_lbl_pairs, c->d_lbl_keys, c->n_pairs, nw, xfit, xscore,
-                                    c->st));
-  HIPCHK(c, ksg_launch_static_fold(const_cast<uint64_t*>(d.static_fit), const_cast<int64_t*>(d.static_score),
-                                   do_fit ? xfit : nullptr, do_score ? xscore : nullptr, nw, N, d.has_static_fit,
-                                   d.has_static_score, c->st));
-  HIPCHK(c, hipStreamSynchronize(c->st));
-  if (do_fit) d.has_static_fit = 1;
-  if (do_score) {
-    d.has_static_score = 1;
-    c->static_mag += mag;
-    if (weighted) d.empty_priorities = 0;
-  }
-  set_wide(c);
-  return KSG_OK;
-}
 
 static int add_pod_impl(ksg_ctx* c, uint32_t host_id, const ksg_pod* pod, const uint32_t* ids) {
   if (int rc0 = flush_deferred(c)) return rc0;
   if (int rs = cluster_ok(c)) return rs;
   int rc = check_pod(c, pod, ids, pod_ids_extent(pod));
   if (rc) return rc;
-  if (host_id < c->N && (rc = note_requests(c, pod, 1))) return rc;
+  if (host_id < c->cl.N && (rc = note_requests(c, pod, 1))) return rc;
   rc = mirror_add(c, host_id, pod, ids, true);
   if (rc) return rc;
   if (c->patches.size() > 4096) return flush_patches(c);
@@ -1480,50 +1054,50 @@ int remove_pod_impl(ksg_ctx* c, uint64_t uid) {
   c->pods.erase(it);
   const uint32_t h = r.host;
   if (c->ext_on) c->ext_scalar.erase(uid);
-  if (h < c->N) {
-    c->used_c[h] = (int64_t)((uint64_t)c->used_c[h] - (uint64_t)r.cpu);
-    c->used_m[h] = (int64_t)((uint64_t)c->used_m[h] - (uint64_t)r.mem);
+  if (h < c->cl.N) {
+    c->mir.used_c[h] = (int64_t)((uint64_t)c->mir.used_c[h] - (uint64_t)r.cpu);
+    c->mir.used_m[h] = (int64_t)((uint64_t)c->mir.used_m[h] - (uint64_t)r.mem);
     c->mu_dirty = true;
-    patch64(c, c->dev.used_cpu + h, c->used_c[h]);
-    patch64(c, c->dev.used_mem + h, c->used_m[h]);
+    patch64(c, c->cl.dev.used_cpu + h, c->mir.used_c[h]);
+    patch64(c, c->cl.dev.used_mem + h, c->mir.used_m[h]);
     if (c->ext_on)
       for (uint32_t q = 0; q < c->ext.n_scalar; ++q) {
         if (!r.scalar[q]) continue;
-        int64_t& u = c->sc_used[(size_t)q * c->N + h];
+        int64_t& u = c->mir.sc_used[(size_t)q * c->cl.N + h];
         u = (int64_t)((uint64_t)u - (uint64_t)r.scalar[q]);
-        patch64(c, c->dev.scalar_used + (size_t)q * c->N + h, u);
+        patch64(c, c->cl.dev.scalar_used + (size_t)q * c->cl.N + h, u);
       }
     for (uint32_t k : r.keys) {
-      auto kit = c->key_ref.find(((uint64_t)k << 32) | h);
-      if (kit != c->key_ref.end() && --kit->second == 0) {
-        c->key_ref.erase(kit);
-        patch_andnot(c, c->dev.keymap + (size_t)k * c->nw + (h >> 6), 1ULL << (h & 63));
+      auto kit = c->mir.key_ref.find(((uint64_t)k << 32) | h);
+      if (kit != c->mir.key_ref.end() && --kit->second == 0) {
+        c->mir.key_ref.erase(kit);
+        patch_andnot(c, c->cl.dev.keymap + (size_t)k * c->cl.nw + (h >> 6), 1ULL << (h & 63));
       }
     }
   }
   for (uint32_t s : r.svcs) {
     int32_t before;
-    if (h < c->N) {
-      int32_t& v = c->svc_cnt[(size_t)s * c->N + h];
+    if (h < c->cl.N) {
+      int32_t& v = c->mir.svc_cnt[(size_t)s * c->cl.N + h];
       before = v--;
-      patch32(c, c->dev.svc_cnt + (size_t)s * c->N + h, v);
-      if (v == 0) patch_andnot(c, c->dev.svc_bits + (size_t)s * c->nw + (h >> 6), 1ULL << (h & 63));
+      patch32(c, c->cl.dev.svc_cnt + (size_t)s * c->cl.N + h, v);
+      if (v == 0) patch_andnot(c, c->cl.dev.svc_bits + (size_t)s * c->cl.nw + (h >> 6), 1ULL << (h & 63));
     } else {
-      auto& m = c->svc_ext[s];
+      auto& m = c->mir.svc_ext[s];
       before = m[h]--;
       if (m[h] == 0) m.erase(h);
     }
-    if (before == c->svc_max[s]) {
-      c->svc_max[s] = recompute_max(c, s);
-      patch32(c, c->dev.svc_max + s, c->svc_max[s]);
+    if (before == c->mir.svc_max[s]) {
+      c->mir.svc_max[s] = recompute_max(c, s);
+      patch32(c, c->cl.dev.svc_max + s, c->mir.svc_max[s]);
     }
-    --c->svc_total[s];
-    patch32(c, c->dev.svc_total + s, c->svc_total[s]);
-    c->svc_members[s].erase(r.seq);
+    --c->mir.svc_total[s];
+    patch32(c, c->cl.dev.svc_total + s, c->mir.svc_total[s]);
+    c->mir.svc_members[s].erase(r.seq);
     const int32_t pc = peer_code(c, s);
-    if (pc != c->svc_peer[s]) {
-      c->svc_peer[s] = pc;
-      patch32(c, c->dev.svc_peer + s, pc);
+    if (pc != c->mir.svc_peer[s]) {
+      c->mir.svc_peer[s] = pc;
+      patch32(c, c->cl.dev.svc_peer + s, pc);
     }
   }
   if (c->patches.size() > 4096) return flush_patches(c);
@@ -1587,7 +1161,7 @@ int ksg_schedule_begin(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, int6
     c->pend_srv = false;
     if (int rq = apply_queued(c)) return rq;
   }
-  if (c->N == 0) return KSG_NONODES;
+  if (c->cl.N == 0) return KSG_NONODES;
   if (c->ext_on && !c->cur_ext) c->ext_scalar.erase(pod->uid);  // (plain entry point: no extension requests)
   const size_t ext = call_ids_extent(c, pod);
   int rc = check_pod(c, pod, ids, ext);
@@ -1605,14 +1179,14 @@ int ksg_schedule_begin(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, int6
     // every requirement given; an unlabelled peer leaves -1, which it resolves to the same -1)
     ksg_pod rp;
     const ksg_pod* sp = pod;
-    if (!c->h_aff_pair.empty() && pod->service >= 0 && (uint32_t)pod->service < c->S) {
-      const int32_t peer = c->svc_peer[pod->service];
+    if (!c->cl.h_aff_pair.empty() && pod->service >= 0 && (uint32_t)pod->service < c->cl.S) {
+      const int32_t peer = c->mir.svc_peer[pod->service];
       bool given = true;
       for (uint32_t j = 0; j < c->cfg.n_aff_labels && j < KSG_MAX_AFF; ++j) given = given && pod->aff_pair[j] != -1;
-      if (!given && peer >= 0 && (uint32_t)peer < c->N) {
+      if (!given && peer >= 0 && (uint32_t)peer < c->cl.N) {
         rp = *pod;
         for (uint32_t j = 0; j < c->cfg.n_aff_labels && j < KSG_MAX_AFF; ++j)
-          if (rp.aff_pair[j] == -1) rp.aff_pair[j] = c->h_aff_pair[(size_t)j * c->N + (uint32_t)peer];
+          if (rp.aff_pair[j] == -1) rp.aff_pair[j] = c->cl.h_aff_pair[(size_t)j * c->cl.N + (uint32_t)peer];
         sp = &rp;
       }
     }
@@ -1625,7 +1199,7 @@ int ksg_schedule_begin(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, int6
       if ((rc = srv_settle(c))) return rc;
       if (r[1] == KSG_SRV_BADREQ) return fail(c, KSG_ERR_STATE, "drop-in server rejected begin request");
       if (r[1] == ~0u) return fail(c, KSG_ERR_NOPEER, "service affinity peer is not on a known node");
-      if (fail_codes) memcpy(fail_codes, c->srv_fail, (size_t)(c->hi - c->lo));
+      if (fail_codes) memcpy(fail_codes, c->srv_fail, (size_t)(c->cl.hi - c->cl.lo));
       const int64_t m = (int64_t)((uint64_t)r[2] | ((uint64_t)r[3] << 32));
       if (max_score) *max_score = r[1] > 0 ? m : 0;
       if (tie_count) *tie_count = r[1];
@@ -1644,17 +1218,17 @@ int ksg_schedule_begin(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, int6
   if ((rc = srv_stop(c))) return rc;
   if ((rc = flush_patches(c))) return rc;
   if ((rc = ensure_map(c)) || (rc = upload_one(c, pod, ids, ext))) return rc;
-  if ((rc = scan_exchange(c, c->one_pod, c->one_ids, KSG_MODE_BEGIN, fail_codes ? c->d_fail : nullptr, nullptr,
+  if ((rc = scan_exchange(c, c->one_pod, c->one_ids, KSG_MODE_BEGIN, fail_codes ? c->cl.d_fail : nullptr, nullptr,
                           c->ext_on ? c->d_one_ext : nullptr)))
     return rc;
-  HIPCHK(c, ksg_launch_decide(c->dev, c->one_pod, c->one_ids, rec_buf(c), c->rec_bytes, c->world,
-                              c->d_shard_wlo, 0, 0, c->d_rng, nullptr, 0, reinterpret_cast<int64_t*>(c->d_map),
+  HIPCHK(c, ksg_launch_decide(c->cl.dev, c->one_pod, c->one_ids, rec_buf(c), c->cl.rec_bytes, c->world,
+                              c->cl.d_shard_wlo, 0, 0, c->d_rng, nullptr, 0, reinterpret_cast<int64_t*>(c->d_map),
                               c->st));
   int64_t summ[3];
-  const size_t nf = fail_codes ? (size_t)(c->hi - c->lo) : 0;
+  const size_t nf = fail_codes ? (size_t)(c->cl.hi - c->cl.lo) : 0;
   if (nf) {
     if ((rc = c->h_dn.grow(c, nf))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_dn, c->d_fail, nf, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipMemcpyAsync(c->h_dn, c->cl.d_fail, nf, hipMemcpyDeviceToHost, c->st));
   }
   HIPCHK(c, hipStreamSynchronize(c->st));
   memcpy(summ, c->h_map, sizeof summ);
@@ -1677,8 +1251,8 @@ static int commit_on_device(ksg_ctx* c, uint32_t tie_index, int32_t* node) {
     c->pend_srv = false;
     // the tie_index-th tie from the top (generic_scheduler.go:88-95) from the begin's tie words
     const int64_t off = srv_pick(c->srv_tw, c->pending_k - 1 - tie_index);
-    if (off < 0 || off >= (int64_t)(c->hi - c->lo)) return fail(c, KSG_ERR_STATE, "commit selected no node");
-    *node = (int32_t)(c->lo + (uint32_t)off);
+    if (off < 0 || off >= (int64_t)(c->cl.hi - c->cl.lo)) return fail(c, KSG_ERR_STATE, "commit selected no node");
+    *node = (int32_t)(c->cl.lo + (uint32_t)off);
     // AssumePod's delta: one control request carrying the pod, not waited for (the next
     // BEGIN's scan waits on the device until it is applied)
     uint32_t hdr[KSG_SRV_HDR_DW] = {KSG_SRV_COMMIT};
@@ -1697,8 +1271,8 @@ static int commit_on_device(ksg_ctx* c, uint32_t tie_index, int32_t* node) {
   if (rc) return rc;
   if ((rc = srv_stop(c))) return rc;
   // the pending pod is still in d_one (begin's upload; nothing re-uploads before the commit)
-  HIPCHK(c, ksg_launch_decide(c->dev, c->one_pod, c->one_ids, rec_buf(c), c->rec_bytes, c->world,
-                              c->d_shard_wlo, 2, tie_index, c->d_rng, reinterpret_cast<int32_t*>(c->d_map + 32), 0,
+  HIPCHK(c, ksg_launch_decide(c->cl.dev, c->one_pod, c->one_ids, rec_buf(c), c->cl.rec_bytes, c->world,
+                              c->cl.d_shard_wlo, 2, tie_index, c->d_rng, reinterpret_cast<int32_t*>(c->d_map + 32), 0,
                               c->d_summary, c->st, c->ext_on ? c->d_one_ext : nullptr));
   HIPCHK(c, hipStreamSynchronize(c->st));
   memcpy(node, c->h_map + 32, 4);
@@ -1733,7 +1307,7 @@ int ksg_evaluate(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, uint8_t* f
   if (int rc0 = flush_deferred(c)) return rc0;
   if (int rs = cluster_ok(c)) return rs;
   HIPCHK(c, hipSetDevice(c->device));
-  if (c->N == 0) return KSG_NONODES;
+  if (c->cl.N == 0) return KSG_NONODES;
   const size_t ext = call_ids_extent(c, pod);
   int rc = check_pod(c, pod, ids, ext);
   if (rc) return rc;
@@ -1743,15 +1317,15 @@ int ksg_evaluate(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, uint8_t* f
   // errors surface through the BEGIN record, so run BEGIN first for the flag
   if ((rc = scan_exchange(c, c->one_pod, c->one_ids, KSG_MODE_BEGIN, nullptr, nullptr, c->ext_on ? c->d_one_ext : nullptr)))
     return rc;
-  HIPCHK(c, ksg_launch_decide(c->dev, c->one_pod, c->one_ids, rec_buf(c), c->rec_bytes, c->world,
-                              c->d_shard_wlo, 0, 0, c->d_rng, nullptr, 0, c->d_summary, c->st));
-  if ((rc = scan_exchange(c, c->one_pod, c->one_ids, KSG_MODE_EVAL, c->d_fail, c->d_score, c->ext_on ? c->d_one_ext : nullptr)))
+  HIPCHK(c, ksg_launch_decide(c->cl.dev, c->one_pod, c->one_ids, rec_buf(c), c->cl.rec_bytes, c->world,
+                              c->cl.d_shard_wlo, 0, 0, c->d_rng, nullptr, 0, c->d_summary, c->st));
+  if ((rc = scan_exchange(c, c->one_pod, c->one_ids, KSG_MODE_EVAL, c->cl.d_fail, c->cl.d_score, c->ext_on ? c->d_one_ext : nullptr)))
     return rc;
   int64_t summ[3];
   HIPCHK(c, hipMemcpyAsync(summ, c->d_summary, sizeof summ, hipMemcpyDeviceToHost, c->st));
-  const size_t ns = c->hi - c->lo;
-  if (fail_out && ns) HIPCHK(c, hipMemcpyAsync(fail_out, c->d_fail, ns, hipMemcpyDeviceToHost, c->st));
-  if (score_out && ns) HIPCHK(c, hipMemcpyAsync(score_out, c->d_score, ns * 8, hipMemcpyDeviceToHost, c->st));
+  const size_t ns = c->cl.hi - c->cl.lo;
+  if (fail_out && ns) HIPCHK(c, hipMemcpyAsync(fail_out, c->cl.d_fail, ns, hipMemcpyDeviceToHost, c->st));
+  if (score_out && ns) HIPCHK(c, hipMemcpyAsync(score_out, c->cl.d_score, ns * 8, hipMemcpyDeviceToHost, c->st));
   HIPCHK(c, hipStreamSynchronize(c->st));
   if (summ[2]) return fail(c, KSG_ERR_NOPEER, "service affinity peer is not on a known node");
   return KSG_OK;
@@ -1780,11 +1354,11 @@ int ksg_debug_counters(ksg_ctx* c, int32_t* out, uint32_t n_words) {
   if (!c || (!out && n_words)) return KSG_ERR_ARG;
   KSG_LOCK(c);
   if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
-  if (!c->dev.dbgbuf) return fail(c, KSG_ERR_STATE, "debug counters need KSG_DEBUG=8 at ksg_create");
+  if (!c->cl.dev.dbgbuf) return fail(c, KSG_ERR_STATE, "debug counters need KSG_DEBUG=8 at ksg_create");
   (void)hipSetDevice(c->device);
   HIPCHK(c, hipStreamSynchronize(c->st));
   int32_t words[KSG_DEBUG_COUNTER_WORDS];
-  HIPCHK(c, hipMemcpy(words, c->dev.dbgbuf, sizeof(words), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(words, c->cl.dev.dbgbuf, sizeof(words), hipMemcpyDeviceToHost));
   for (uint32_t k = 0; k < n_words; ++k) out[k] = k < KSG_DEBUG_COUNTER_WORDS ? words[k] : 0;
   return KSG_OK;
 }
@@ -1792,8 +1366,8 @@ int ksg_debug_counters(ksg_ctx* c, int32_t* out, uint32_t n_words) {
 int ksg_shard(ksg_ctx* c, uint32_t* lo, uint32_t* hi) {
   if (!c) return KSG_ERR_ARG;
   KSG_LOCK(c);
-  if (lo) *lo = c->lo;
-  if (hi) *hi = c->hi;
+  if (lo) *lo = c->cl.lo;
+  if (hi) *hi = c->cl.hi;
   return KSG_OK;
 }
 
@@ -1804,9 +1378,9 @@ int ksg_read_requested(ksg_ctx* c, int64_t* milli_cpu, int64_t* memory) {
   HIPCHK(c, hipSetDevice(c->device));
   int rc = flush_patches(c);
   if (rc) return rc;
-  if (c->N) {
-    if (milli_cpu) HIPCHK(c, hipMemcpyAsync(milli_cpu, c->dev.used_cpu, c->N * 8, hipMemcpyDeviceToHost, c->st));
-    if (memory) HIPCHK(c, hipMemcpyAsync(memory, c->dev.used_mem, c->N * 8, hipMemcpyDeviceToHost, c->st));
+  if (c->cl.N) {
+    if (milli_cpu) HIPCHK(c, hipMemcpyAsync(milli_cpu, c->cl.dev.used_cpu, c->cl.N * 8, hipMemcpyDeviceToHost, c->st));
+    if (memory) HIPCHK(c, hipMemcpyAsync(memory, c->cl.dev.used_mem, c->cl.N * 8, hipMemcpyDeviceToHost, c->st));
   }
   HIPCHK(c, hipStreamSynchronize(c->st));
   return KSG_OK;
@@ -1822,16 +1396,16 @@ int ksg_read_state(ksg_ctx* c, uint64_t* keymap, int32_t* svc_cnt, uint64_t* svc
   HIPCHK(c, hipSetDevice(c->device));
   int rc = flush_patches(c);
   if (rc) return rc;
-  const size_t K = c->cfg.max_conflict_keys, S = c->S, N = c->N, nw = c->nw;
+  const size_t K = c->cfg.max_conflict_keys, S = c->cl.S, N = c->cl.N, nw = c->cl.nw;
   auto out = [&](void* dst, const void* src, size_t bytes) {
     return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->st) : hipSuccess;
   };
-  HIPCHK(c, out(keymap, c->dev.keymap, K * nw * 8));
-  HIPCHK(c, out(svc_cnt, c->dev.svc_cnt, S * N * 4));
-  HIPCHK(c, out(svc_bits, c->dev.svc_bits, S * nw * 8));
-  HIPCHK(c, out(svc_max, c->dev.svc_max, S * 4));
-  HIPCHK(c, out(svc_total, c->dev.svc_total, S * 4));
-  HIPCHK(c, out(svc_peer, c->dev.svc_peer, S * 4));
+  HIPCHK(c, out(keymap, c->cl.dev.keymap, K * nw * 8));
+  HIPCHK(c, out(svc_cnt, c->cl.dev.svc_cnt, S * N * 4));
+  HIPCHK(c, out(svc_bits, c->cl.dev.svc_bits, S * nw * 8));
+  HIPCHK(c, out(svc_max, c->cl.dev.svc_max, S * 4));
+  HIPCHK(c, out(svc_total, c->cl.dev.svc_total, S * 4));
+  HIPCHK(c, out(svc_peer, c->cl.dev.svc_peer, S * 4));
   HIPCHK(c, hipStreamSynchronize(c->st));
   return KSG_OK;
 }
@@ -1901,407 +1475,6 @@ int ksg_set_extensions(ksg_ctx* c, const ksg_ext_config* e) {
     return fail(c, KSG_ERR_ARG, "extensions: bad filters / n_scalar");
   c->ext = *e;
   c->ext_on = e->filters || e->w_taint_toleration || e->w_balanced || e->n_scalar;
-  return KSG_OK;
-}
-
-static int node_ext_upload(ksg_ctx* c, uint32_t n_nodes, const int64_t* scalar_cap, const uint32_t* taint_off,
-                           const uint32_t* taint_n, const uint32_t* taint_ids, uint32_t n_taint_ids);
-
-int ksg_set_node_ext(ksg_ctx* c, uint32_t n_nodes, const int64_t* scalar_cap, const uint32_t* taint_off,
-                     const uint32_t* taint_n, const uint32_t* taint_ids, uint32_t n_taint_ids) {
-  if (!c) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
-  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
-  if (!c->ext_on) return fail(c, KSG_ERR_STATE, "ksg_set_node_ext: extensions are off");
-  if (!c->have_cluster || n_nodes != c->N) return fail(c, KSG_ERR_ARG, "ksg_set_node_ext: node count != cluster");
-  if (int rc0 = flush_deferred(c)) return rc0;
-  if (!c->pods.empty()) return fail(c, KSG_ERR_STATE, "ksg_set_node_ext: call before adding pods");
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = node_ext_upload(c, n_nodes, scalar_cap, taint_off, taint_n, taint_ids, n_taint_ids)) return rc;
-  c->sc_used.assign((size_t)c->ext.n_scalar * c->N, 0);
-  return KSG_OK;
-}
-
-// ksg_set_node_ext's arrays into the device tables of the context's node list (n_nodes == N):
-// scalar_cap, taintmap, ntaint; scalar_used zeroed
-static int node_ext_upload(ksg_ctx* c, uint32_t n_nodes, const int64_t* scalar_cap, const uint32_t* taint_off,
-                           const uint32_t* taint_n, const uint32_t* taint_ids, uint32_t n_taint_ids) {
-  const size_t NN = std::max<uint32_t>(c->N, 1);
-  if (c->ext.n_scalar && n_nodes) {
-    if (!scalar_cap) return fail(c, KSG_ERR_ARG, "ksg_set_node_ext: scalar_cap missing");
-    HIPCHK(c, hipMemcpyAsync(const_cast<int64_t*>(c->dev.scalar_cap), scalar_cap, (size_t)c->ext.n_scalar * n_nodes * 8,
-                             hipMemcpyHostToDevice, c->st));
-  }
-  std::vector<uint64_t> tm((size_t)std::max<uint32_t>(c->ext.max_taints, 1) * std::max<uint32_t>(c->nw, 1), 0);
-  if (taint_off && taint_n)
-    for (uint32_t n = 0; n < n_nodes; ++n)
-      for (uint32_t i = 0; i < taint_n[n]; ++i) {
-        if ((size_t)taint_off[n] + i >= n_taint_ids || !taint_ids) return fail(c, KSG_ERR_ARG, "taint list out of range");
-        const uint32_t t = taint_ids[taint_off[n] + i];
-        if (t >= c->ext.max_taints) return fail(c, KSG_ERR_CAPACITY, "taint id %u >= max_taints", t);
-        tm[(size_t)t * c->nw + (n >> 6)] |= 1ULL << (n & 63);
-      }
-  HIPCHK(c, hipMemcpyAsync(const_cast<uint64_t*>(c->dev.taintmap), tm.data(), tm.size() * 8, hipMemcpyHostToDevice,
-                           c->st));
-  if (c->dev.ntaint) {  // the same taints as one mask per node (taint ids < 64)
-    std::vector<uint64_t> ntm(std::max<uint32_t>(n_nodes, 1), 0);
-    if (taint_off && taint_n)
-      for (uint32_t n = 0; n < n_nodes; ++n)
-        for (uint32_t i = 0; i < taint_n[n]; ++i) ntm[n] |= 1ULL << (taint_ids[taint_off[n] + i] & 63);
-    HIPCHK(c, hipMemcpyAsync(const_cast<uint64_t*>(c->dev.ntaint), ntm.data(), ntm.size() * 8, hipMemcpyHostToDevice,
-                             c->st));
-  }
-  HIPCHK(c, hipMemsetAsync(c->dev.scalar_used, 0, (size_t)std::max<uint32_t>(c->ext.n_scalar, 1) * NN * 8, c->st));
-  HIPCHK(c, hipStreamSynchronize(c->st));
-  return KSG_OK;
-}
-
-int ksg_read_ext_used(ksg_ctx* c, int64_t* used) {
-  if (!c || !used || !c->have_cluster) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (!c->ext_on) return fail(c, KSG_ERR_STATE, "ksg_read_ext_used: extensions are off");
-  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = flush_patches(c)) return rc;
-  const size_t nb = (size_t)c->ext.n_scalar * c->N * 8;
-  if (nb) HIPCHK(c, hipMemcpyAsync(used, c->dev.scalar_used, nb, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(c, hipStreamSynchronize(c->st));
-  return KSG_OK;
-}
-
-// ---- ksg_update_cluster: a new node list under the same pods (ksg_remap.hip) ------------
-// What build_cluster writes in the context. ksg_update_cluster puts the old list's parts in one
-// of these, builds the new list's beside them (the gather reads the old arrays and writes the
-// new ones), and either drops the old parts or, on any failure, swaps them back: a refused call
-// leaves the context as it was. Whatever the object holds at the end is freed with it.
-extern "C++" {
-namespace {
-struct ClusterParts {
-  uint32_t N = 0, nw = 0, n_pairs = 0, S = 0, D = 0, lo = 0, hi = 0, wlo = 0, nwords = 0, nwords_max = 0;
-  std::vector<uint32_t> shard_wlo_h;
-  int R = 1;
-  size_t lds = 0;
-  KsgDev dev{};
-  std::vector<void*> cluster_allocs;
-  DevBuf<uint32_t> d_shard_wlo;
-  DevBuf<int32_t> dbgbuf, d_dpart, d_dglobal;
-  DevBuf<uint8_t> d_fail, d_rec_send, d_rec_recv;
-  DevBuf<int64_t> d_score;
-  uint32_t rec_bytes = 0, dbg_corrupt = 0;
-  uint64_t* d_zmap = nullptr;
-  std::vector<int32_t> h_aff_pair;
-  int64_t max_cap = 0, min_cap = 0;
-  bool lr_wild = false, win_d1 = true;
-  unsigned __int128 static_mag = 0;
-  const ksg_node* d_lbl_nodes = nullptr;
-  const uint32_t* d_lbl_pairs = nullptr;
-  const uint32_t* d_lbl_keys = nullptr;
-  ~ClusterParts() {
-    for (void* p : cluster_allocs) (void)hipFree(p);
-  }
-};
-
-template <typename T>
-void swap_buf(DevBuf<T>& a, DevBuf<T>& b) {
-  std::swap(a.p, b.p);
-  std::swap(a.cap, b.cap);
-}
-
-void swap_parts(ksg_ctx* c, ClusterParts& s) {
-  std::swap(c->N, s.N);
-  std::swap(c->nw, s.nw);
-  std::swap(c->n_pairs, s.n_pairs);
-  std::swap(c->S, s.S);
-  std::swap(c->D, s.D);
-  std::swap(c->lo, s.lo);
-  std::swap(c->hi, s.hi);
-  std::swap(c->wlo, s.wlo);
-  std::swap(c->nwords, s.nwords);
-  std::swap(c->nwords_max, s.nwords_max);
-  std::swap(c->shard_wlo_h, s.shard_wlo_h);
-  std::swap(c->R, s.R);
-  std::swap(c->lds, s.lds);
-  std::swap(c->dev, s.dev);
-  std::swap(c->cluster_allocs, s.cluster_allocs);
-  swap_buf(c->d_shard_wlo, s.d_shard_wlo);
-  swap_buf(c->dbgbuf, s.dbgbuf);
-  swap_buf(c->d_dpart, s.d_dpart);
-  swap_buf(c->d_dglobal, s.d_dglobal);
-  swap_buf(c->d_fail, s.d_fail);
-  swap_buf(c->d_rec_send, s.d_rec_send);
-  swap_buf(c->d_rec_recv, s.d_rec_recv);
-  swap_buf(c->d_score, s.d_score);
-  std::swap(c->rec_bytes, s.rec_bytes);
-  std::swap(c->dbg_corrupt, s.dbg_corrupt);
-  std::swap(c->d_zmap, s.d_zmap);
-  std::swap(c->h_aff_pair, s.h_aff_pair);
-  std::swap(c->max_cap, s.max_cap);
-  std::swap(c->min_cap, s.min_cap);
-  std::swap(c->lr_wild, s.lr_wild);
-  std::swap(c->win_d1, s.win_d1);
-  std::swap(c->static_mag, s.static_mag);
-  std::swap(c->d_lbl_nodes, s.d_lbl_nodes);
-  std::swap(c->d_lbl_pairs, s.d_lbl_pairs);
-  std::swap(c->d_lbl_keys, s.d_lbl_keys);
-}
-
-// the host mirror of the new list, computed beside the old one and installed after the device work
-struct NewMirror {
-  std::vector<int64_t> used_c, used_m, sc_used;
-  std::vector<int32_t> svc_cnt, svc_max, svc_peer, outside_max;
-  std::unordered_map<uint64_t, uint32_t> key_ref;
-  std::vector<std::unordered_map<uint32_t, int32_t>> svc_ext;
-  std::vector<std::map<uint64_t, uint32_t>> svc_members;
-  std::vector<std::pair<PodRec*, uint32_t>> moved;  // pods whose host id changes
-};
-
-double us_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-}
-}  // namespace
-}  // extern "C++"
-
-// The device half, with the new list's arrays in c->dev and the old list's in old.dev: the
-// gather by src, the svc kernel, then the joined hosts' pods as patches (nm has their values).
-static int remap_device(ksg_ctx* c, const ClusterParts& old, const std::vector<int32_t>& src, const NewMirror& nm) {
-  const uint32_t N = c->N, S = c->S, K = c->cfg.max_conflict_keys;
-  struct Scratch {
-    int32_t* p = nullptr;
-    ~Scratch() {
-      if (p) (void)hipFree(p);
-    }
-  } tmp;
-  const size_t words = (size_t)N + 2 * (size_t)S;
-  HIPCHK(c, hipMalloc((void**)&tmp.p, std::max<size_t>(words, 1) * sizeof(int32_t)));
-  int32_t *d_src = tmp.p, *d_omax = tmp.p + N, *d_peer = d_omax + S;
-  if (N) HIPCHK(c, hipMemcpyAsync(d_src, src.data(), (size_t)N * 4, hipMemcpyHostToDevice, c->st));
-  if (S) {
-    HIPCHK(c, hipMemcpyAsync(d_omax, nm.outside_max.data(), (size_t)S * 4, hipMemcpyHostToDevice, c->st));
-    HIPCHK(c, hipMemcpyAsync(d_peer, nm.svc_peer.data(), (size_t)S * 4, hipMemcpyHostToDevice, c->st));
-  }
-  const KsgDev &o = old.dev, &d = c->dev;
-  HIPCHK(c, hipEventRecord(c->ev0, c->st));
-  HIPCHK(c, ksg_launch_remap_rows64(o.used_cpu, d.used_cpu, d_src, old.N, N, 1, c->st));
-  HIPCHK(c, ksg_launch_remap_rows64(o.used_mem, d.used_mem, d_src, old.N, N, 1, c->st));
-  if (c->ext_on && c->ext.n_scalar)
-    HIPCHK(c, ksg_launch_remap_rows64(o.scalar_used, d.scalar_used, d_src, old.N, N, c->ext.n_scalar, c->st));
-  HIPCHK(c, ksg_launch_remap_rows32(o.svc_cnt, d.svc_cnt, d_src, old.N, N, S, c->st));
-  HIPCHK(c, ksg_launch_remap_bits(o.keymap, d.keymap, d_src, old.nw, c->nw, N, K, c->st));
-  HIPCHK(c, ksg_launch_remap_bits(o.svc_bits, d.svc_bits, d_src, old.nw, c->nw, N, S, c->st));
-  HIPCHK(c, ksg_launch_remap_svc(d.svc_cnt, N, S, d_omax, d_peer, o.svc_total, d.svc_max, d.svc_total, d.svc_peer, c->st));
-  HIPCHK(c, hipEventRecord(c->ev1, c->st));
-  if (int rc = flush_patches(c)) return rc;  // (the joined hosts' pods; synchronises when there are any)
-  HIPCHK(c, hipStreamSynchronize(c->st));
-  float ms = 0.f;
-  HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->last_update_ms = ms;
-  return KSG_OK;
-}
-
-static int update_cluster_impl(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const uint32_t* node_pairs,
-                               uint32_t n_node_pairs, const uint32_t* pair_keys, uint32_t n_pairs,
-                               const uint32_t* old_to_new, const uint32_t* outside_old, const uint32_t* outside_new,
-                               uint32_t n_outside, const ksg_node_ext_arrays* ext) {
-  const auto t0 = std::chrono::steady_clock::now();
-  if (int rs = cluster_ok(c)) return rs;
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
-  if (ext && !c->ext_on) return fail(c, KSG_ERR_STATE, "ksg_update_cluster: ext given, extensions are off");
-  if (!ext && c->ext_on) return fail(c, KSG_ERR_ARG, "ksg_update_cluster: extensions are on, ext == NULL");
-  // (what the arguments alone decide comes first: such a refusal does not even stop the server)
-  if (n_pairs == 0) n_pairs = 1;  // pair 0 always exists (empty)
-  if (int rc = check_nodes(c, nodes, n_nodes, node_pairs, n_node_pairs, n_pairs)) return rc;
-  const uint32_t oldN = c->N, S = c->S;
-  if (n_nodes > (uint32_t)INT32_MAX) return fail(c, KSG_ERR_CAPACITY, "ksg_update_cluster: %u nodes", n_nodes);
-  if (oldN && !old_to_new) return fail(c, KSG_ERR_ARG, "ksg_update_cluster: old_to_new == NULL with %u old nodes", oldN);
-  if (n_outside && (!outside_old || !outside_new))
-    return fail(c, KSG_ERR_ARG, "ksg_update_cluster: outside arrays missing");
-  // the renaming: injective over the old ranks and the listed outside hosts
-  std::unordered_map<uint32_t, uint32_t> omap;
-  std::unordered_set<uint32_t> taken;
-  omap.reserve(n_outside);
-  taken.reserve((size_t)oldN + n_outside);
-  for (uint32_t r = 0; r < oldN; ++r)
-    if (!taken.insert(old_to_new[r]).second)
-      return fail(c, KSG_ERR_ARG, "ksg_update_cluster: new host id %u given twice", old_to_new[r]);
-  for (uint32_t j = 0; j < n_outside; ++j) {
-    if (outside_old[j] < oldN)
-      return fail(c, KSG_ERR_ARG, "ksg_update_cluster: outside_old[%u] = %u is a rank of the old list", j, outside_old[j]);
-    if (!omap.emplace(outside_old[j], outside_new[j]).second)
-      return fail(c, KSG_ERR_ARG, "ksg_update_cluster: outside host %u listed twice", outside_old[j]);
-    if (!taken.insert(outside_new[j]).second)
-      return fail(c, KSG_ERR_ARG, "ksg_update_cluster: new host id %u given twice", outside_new[j]);
-  }
-  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
-  HIPCHK(c, hipSetDevice(c->device));
-  // the mirror is complete and the device equals it
-  if (int rc = flush_deferred(c)) return rc;
-  if (int rc = flush_patches(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->st));
-  for (const auto& kv : c->pods)
-    if (kv.second.host >= oldN && !omap.count(kv.second.host))
-      return fail(c, KSG_ERR_ARG, "ksg_update_cluster: pod %llu is on outside host %u, which is not listed",
-                  (unsigned long long)kv.first, kv.second.host);
-  // src: the old rank behind each new rank (every entry < oldN, so no kernel reads outside a row)
-  std::vector<int32_t> src(n_nodes, -1);
-  for (uint32_t r = 0; r < oldN; ++r)
-    if (old_to_new[r] < n_nodes) src[old_to_new[r]] = (int32_t)r;
-  auto renamed = [&](uint32_t h) { return h < oldN ? old_to_new[h] : omap.find(h)->second; };
-  const double us_valid = us_since(t0);
-
-  // ---- the new list's tables beside the old one's ----
-  const auto t1 = std::chrono::steady_clock::now();
-  ClusterParts old;
-  swap_parts(c, old);
-  auto refuse = [&](int rc) {
-    swap_parts(c, old);  // (the new list's parts leave with `old`)
-    c->patches.clear();
-    return rc;
-  };
-  if (int rc = build_cluster(c, nodes, n_nodes, node_pairs, n_node_pairs, pair_keys, n_pairs, S)) return refuse(rc);
-  if (ext)
-    if (int rc = node_ext_upload(c, n_nodes, ext->scalar_cap, ext->taint_off, ext->taint_n, ext->taint_ids, ext->n_taint_ids))
-      return refuse(rc);
-
-  // ---- the new mirror: survivors' rows by src, then one walk over the pods ----
-  const auto t2 = std::chrono::steady_clock::now();
-  const uint32_t N = n_nodes, nsc = c->ext_on ? c->ext.n_scalar : 0;
-  NewMirror nm;
-  nm.used_c.assign(N, 0);
-  nm.used_m.assign(N, 0);
-  nm.sc_used.assign((size_t)c->ext.n_scalar * N, 0);
-  nm.svc_cnt.assign((size_t)S * N, 0);
-  nm.svc_max.assign(S, 0);
-  nm.outside_max.assign(S, 0);
-  nm.svc_peer.assign(S, -1);
-  nm.svc_ext.assign(S, {});
-  nm.svc_members.assign(S, {});
-  for (uint32_t n = 0; n < N; ++n)
-    if (src[n] >= 0) {
-      nm.used_c[n] = c->used_c[src[n]];
-      nm.used_m[n] = c->used_m[src[n]];
-    }
-  for (uint32_t q = 0; q < nsc; ++q)
-    for (uint32_t n = 0; n < N; ++n)
-      if (src[n] >= 0) nm.sc_used[(size_t)q * N + n] = c->sc_used[(size_t)q * oldN + src[n]];
-  for (uint32_t s = 0; s < S; ++s) {
-    const int32_t* from = c->svc_cnt.data() + (size_t)s * oldN;
-    int32_t* to = nm.svc_cnt.data() + (size_t)s * N;
-    int32_t m = 0;
-    for (uint32_t n = 0; n < N; ++n)
-      if (src[n] >= 0) m = std::max(m, to[n] = from[src[n]]);
-    nm.svc_max[s] = m;
-  }
-  nm.key_ref.reserve(c->key_ref.size());
-  for (const auto& kv : c->key_ref) {
-    const uint32_t t = old_to_new[(uint32_t)kv.first];
-    if (t < N) nm.key_ref[(kv.first & 0xffffffff00000000ull) | t] = kv.second;
-  }
-  const KsgDev& d = c->dev;
-  bool joined_wild = false;         // a joined host's pod would have set lr_wild in the fresh context
-  int64_t joined_hi = c->used_hi;   // ... and the largest total it would have seen (used_hi only grows)
-  for (auto& kv : c->pods) {
-    PodRec& r = kv.second;
-    const uint32_t t = renamed(r.host);
-    if (t != r.host) nm.moved.emplace_back(&r, t);
-    if (t >= N) {  // outside the new list: counted by svc_max alone
-      for (uint32_t s : r.svcs) nm.outside_max[s] = std::max(nm.outside_max[s], ++nm.svc_ext[s][t]);
-      continue;
-    }
-    if (r.host < oldN) continue;  // (a survivor: its rows were gathered)
-    // a host that joined the list: its pods onto the node, as mirror_add would (values for the patches).
-    // On an outside host note_requests never saw them (ksg_add_pod checks node hosts only); the fresh
-    // context re-adds them on a node, so a negative request or a total that could wrap turns it wide.
-    joined_wild = joined_wild || r.cpu < 0 || r.mem < 0 ||
-                  (unsigned __int128)(uint64_t)std::max<int64_t>(joined_hi, 0) + (uint64_t)std::max<int64_t>(std::max(r.cpu, r.mem), 0) >
-                      (unsigned __int128)INT64_MAX;
-    nm.used_c[t] = (int64_t)((uint64_t)nm.used_c[t] + (uint64_t)r.cpu);
-    nm.used_m[t] = (int64_t)((uint64_t)nm.used_m[t] + (uint64_t)r.mem);
-    joined_hi = std::max(joined_hi, std::max(nm.used_c[t], nm.used_m[t]));
-    patch64(c, d.used_cpu + t, nm.used_c[t]);
-    patch64(c, d.used_mem + t, nm.used_m[t]);
-    for (uint32_t q = 0; q < nsc; ++q) {
-      if (!r.scalar[q]) continue;
-      int64_t& u = nm.sc_used[(size_t)q * N + t];
-      u = (int64_t)((uint64_t)u + (uint64_t)r.scalar[q]);
-      patch64(c, d.scalar_used + (size_t)q * N + t, u);
-    }
-    for (uint32_t k : r.keys)
-      if (++nm.key_ref[((uint64_t)k << 32) | t] == 1) patch_or(c, d.keymap + (size_t)k * c->nw + (t >> 6), 1ULL << (t & 63));
-    for (uint32_t s : r.svcs) {
-      const int32_t v = ++nm.svc_cnt[(size_t)s * N + t];
-      patch32(c, d.svc_cnt + (size_t)s * N + t, v);
-      if (v == 1) patch_or(c, d.svc_bits + (size_t)s * c->nw + (t >> 6), 1ULL << (t & 63));
-      nm.svc_max[s] = std::max(nm.svc_max[s], v);
-    }
-  }
-  for (uint32_t s = 0; s < S; ++s) {
-    for (const auto& m : c->svc_members[s]) nm.svc_members[s].emplace_hint(nm.svc_members[s].end(), m.first, renamed(m.second));
-    if (!nm.svc_members[s].empty()) {
-      const uint32_t h = nm.svc_members[s].begin()->second;
-      nm.svc_peer[s] = h < N ? (int32_t)h : -2;
-    }
-    nm.svc_max[s] = std::max(nm.svc_max[s], nm.outside_max[s]);
-  }
-  // (the svc kernel sees the gathered counts only: the joined hosts' maxima go with their patches)
-  if (!c->patches.empty())
-    for (uint32_t s = 0; s < S; ++s) patch32(c, d.svc_max + s, nm.svc_max[s]);
-  double us_mirror = us_since(t2);
-
-  // ---- the device work; then the new list is in force ----
-  const auto t3 = std::chrono::steady_clock::now();
-  if (int rc = remap_device(c, old, src, nm)) return refuse(rc);
-  const double us_dev = std::chrono::duration<double, std::micro>(t2 - t1).count() + us_since(t3);
-  const auto t4 = std::chrono::steady_clock::now();
-  for (auto& mv : nm.moved) mv.first->host = mv.second;
-  c->used_c = std::move(nm.used_c);
-  c->used_m = std::move(nm.used_m);
-  c->sc_used = std::move(nm.sc_used);
-  c->svc_cnt = std::move(nm.svc_cnt);
-  c->svc_max = std::move(nm.svc_max);
-  c->svc_peer = std::move(nm.svc_peer);
-  c->key_ref = std::move(nm.key_ref);
-  c->svc_ext = std::move(nm.svc_ext);
-  c->svc_members = std::move(nm.svc_members);
-  // the score path: never narrower than the fresh context's (the sticky causes stay, the
-  // capacities' were recomputed by build_cluster, the used-total bounds are recomputed on use)
-  c->lr_wild = c->lr_wild || old.lr_wild || joined_wild;
-  c->used_hi = std::max(c->used_hi, joined_hi);
-  for (uint32_t n = 0; n < N; ++n) c->used_hi = std::max(c->used_hi, std::max(c->used_c[n], c->used_m[n]));
-  c->mu_dirty = true;
-  set_wide(c);
-  c->ppw_est = 0.0;
-  us_mirror += us_since(t4);
-  c->last_update_us[0] = us_valid;
-  c->last_update_us[1] = us_dev;
-  c->last_update_us[2] = us_mirror;
-  return KSG_OK;
-}
-
-int ksg_update_cluster(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nodes, const uint32_t* node_pairs,
-                       uint32_t n_node_pairs, const uint32_t* pair_keys, uint32_t n_pairs, const uint32_t* old_to_new,
-                       const uint32_t* outside_old, const uint32_t* outside_new, uint32_t n_outside,
-                       const ksg_node_ext_arrays* ext) {
-  if (!c) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  const int rc = update_cluster_impl(c, nodes, n_nodes, node_pairs, n_node_pairs, pair_keys, n_pairs, old_to_new,
-                                     outside_old, outside_new, n_outside, ext);
-  // a HIP error at any point: the device may not be what the mirror says (as after a failed batch)
-  if (rc == KSG_ERR_HIP && c->have_cluster) c->diverged = true;
-  return rc;
-}
-
-int ksg_last_update_ms(ksg_ctx* c, double* ms) {
-  if (!c || !ms) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  *ms = c->last_update_ms;
-  return KSG_OK;
-}
-
-int ksg_last_update_host_us(ksg_ctx* c, double* us3) {
-  if (!c || !us3) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  for (int i = 0; i < 3; ++i) us3[i] = c->last_update_us[i];
   return KSG_OK;
 }
 
@@ -2415,16 +1588,16 @@ int ksg_explain_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, u
   uint32_t* d_hist = reinterpret_cast<uint32_t*>(c->d_xhist.p);
   uint8_t* d_err = c->d_xhist + hb;
   HIPCHK(c, hipMemsetAsync(c->d_xhist, 0, hb + n, c->st));
-  const uint32_t per = query_per(kExplainStageBytes, codes ? c->N : 0, KSG_EXPLAIN_CHUNK, n);
-  if (codes && (rc = c->d_xcodes.grow(c, (size_t)per * c->N))) return rc;
+  const uint32_t per = query_per(kExplainStageBytes, codes ? c->cl.N : 0, KSG_EXPLAIN_CHUNK, n);
+  if (codes && (rc = c->d_xcodes.grow(c, (size_t)per * c->cl.N))) return rc;
   const auto launch = [&](uint32_t a, uint32_t m) {
-    HIPCHK(c, ksg_launch_explain(c->dev, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m,
+    HIPCHK(c, ksg_launch_explain(c->cl.dev, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m,
                                  codes ? c->d_xcodes : nullptr, d_hist + (size_t)a * KSG_EXPLAIN_SLOTS, d_err + a, c->st));
     return KSG_OK;
   };
   const auto copies = [&](uint32_t a, uint32_t m, bool last) {
     if (codes)
-      HIPCHK(c, hipMemcpyAsync(codes + (size_t)a * c->N, c->d_xcodes, (size_t)m * c->N, hipMemcpyDeviceToHost, c->st));
+      HIPCHK(c, hipMemcpyAsync(codes + (size_t)a * c->cl.N, c->d_xcodes, (size_t)m * c->cl.N, hipMemcpyDeviceToHost, c->st));
     if (last) {  // straight into the caller's arrays
       HIPCHK(c, hipMemcpyAsync(hist, d_hist, hb, hipMemcpyDeviceToHost, c->st));
       HIPCHK(c, hipMemcpyAsync(err, d_err, n, hipMemcpyDeviceToHost, c->st));
@@ -2463,25 +1636,25 @@ int ksg_prioritize_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext
   uint8_t* const po = c->d_pout;
   // pods per launch: the normalised terms, tile partials and candidates of a chunk, and its
   // per-node scores where asked for, each within the staging budget
-  const size_t T = (c->nw + KSG_PRIO_WAVES - 1) / KSG_PRIO_WAVES, D1 = (size_t)c->dev.n_domains_total + 1;
+  const size_t T = (c->cl.nw + KSG_PRIO_WAVES - 1) / KSG_PRIO_WAVES, D1 = (size_t)c->cl.dev.n_domains_total + 1;
   const size_t bpp = D1 * 4 + T * (sizeof(KsgPrioPart) + (size_t)top * 12);
-  const uint32_t per = query_per(kExplainStageBytes, scores ? std::max(bpp, (size_t)c->N * 8) : bpp, KSG_EXPLAIN_CHUNK, n);
+  const uint32_t per = query_per(kExplainStageBytes, scores ? std::max(bpp, (size_t)c->cl.N * 8) : bpp, KSG_EXPLAIN_CHUNK, n);
   const size_t o_part = ((size_t)per * D1 * 4 + 15) & ~(size_t)15, o_cs = o_part + (size_t)per * T * sizeof(KsgPrioPart);
   const size_t o_cn = o_cs + (size_t)per * T * top * 8;
   if ((rc = c->d_ppart.grow(c, o_cn + (size_t)per * T * top * 4))) return rc;
-  if (scores && (rc = c->d_pscores.grow(c, (size_t)per * c->N))) return rc;
+  if (scores && (rc = c->d_pscores.grow(c, (size_t)per * c->cl.N))) return rc;
   int32_t* const dnorm = reinterpret_cast<int32_t*>(c->d_ppart.p);
   KsgPrioPart* const part = reinterpret_cast<KsgPrioPart*>(c->d_ppart + o_part);
   int64_t* const cs = reinterpret_cast<int64_t*>(c->d_ppart + o_cs);
   int32_t* const cn = reinterpret_cast<int32_t*>(c->d_ppart + o_cn);
-  const bool reduce = ksg_prio_needs_reduce(c->dev, ext != nullptr);
+  const bool reduce = ksg_prio_needs_reduce(c->cl.dev, ext != nullptr);
   const auto launch = [&](uint32_t a, uint32_t m) {
     const ksg_pod_ext* xa = dext ? dext + a : nullptr;
     HIPCHK(c, hipMemsetAsync(dnorm, 0, (size_t)m * D1 * 4, c->st));
-    if (reduce) HIPCHK(c, ksg_launch_prio_reduce(c->dev, c->d_pods + a, xa, c->d_ids, m, dnorm, c->st));
-    HIPCHK(c, ksg_launch_prio_score(c->dev, c->d_pods + a, xa, c->d_ids, m, top, dnorm,
+    if (reduce) HIPCHK(c, ksg_launch_prio_reduce(c->cl.dev, c->d_pods + a, xa, c->d_ids, m, dnorm, c->st));
+    HIPCHK(c, ksg_launch_prio_score(c->cl.dev, c->d_pods + a, xa, c->d_ids, m, top, dnorm,
                                     scores ? c->d_pscores.p : nullptr, part, cs, cn, po + o_err + a, c->st));
-    HIPCHK(c, ksg_launch_prio_merge(c->dev, m, top, part, cs, cn, reinterpret_cast<int64_t*>(po) + a,
+    HIPCHK(c, ksg_launch_prio_merge(c->cl.dev, m, top, part, cs, cn, reinterpret_cast<int64_t*>(po) + a,
                                     reinterpret_cast<uint32_t*>(po + o_tie) + a, reinterpret_cast<uint32_t*>(po + o_fit) + a,
                                     reinterpret_cast<int32_t*>(po + o_tn) + (size_t)a * top,
                                     reinterpret_cast<int64_t*>(po + o_ts) + (size_t)a * top, c->st));
@@ -2489,7 +1662,7 @@ int ksg_prioritize_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext
   };
   const auto copies = [&](uint32_t a, uint32_t m, bool last) {
     if (scores)
-      HIPCHK(c, hipMemcpyAsync(scores + (size_t)a * c->N, c->d_pscores, (size_t)m * c->N * 8, hipMemcpyDeviceToHost, c->st));
+      HIPCHK(c, hipMemcpyAsync(scores + (size_t)a * c->cl.N, c->d_pscores, (size_t)m * c->cl.N * 8, hipMemcpyDeviceToHost, c->st));
     if (last) HIPCHK(c, hipMemcpyAsync(c->h_dn, po, ob, hipMemcpyDeviceToHost, c->st));
     return KSG_OK;
   };
@@ -2534,10 +1707,10 @@ int ksg_headroom_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, 
   if ((rc = c->d_hout.grow(c, ob)) || (rc = c->h_dn.grow(c, ob))) return rc;
   uint8_t* const ho = c->d_hout;
   HIPCHK(c, hipMemsetAsync(ho, 0, ob, c->st));
-  const uint32_t per = query_per(c->headroom_stage, counts ? (size_t)c->N * sizeof(uint32_t) : 0, KSG_HEADROOM_CHUNK, n);
-  if (counts && (rc = c->d_hcounts.grow(c, (size_t)per * c->N))) return rc;
+  const uint32_t per = query_per(c->headroom_stage, counts ? (size_t)c->cl.N * sizeof(uint32_t) : 0, KSG_HEADROOM_CHUNK, n);
+  if (counts && (rc = c->d_hcounts.grow(c, (size_t)per * c->cl.N))) return rc;
   const auto launch = [&](uint32_t a, uint32_t m) {
-    HIPCHK(c, ksg_launch_headroom(c->dev, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m, limit, c->headroom_div,
+    HIPCHK(c, ksg_launch_headroom(c->cl.dev, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m, limit, c->headroom_div,
                                   counts ? c->d_hcounts.p : nullptr, reinterpret_cast<uint64_t*>(ho) + a,
                                   reinterpret_cast<uint32_t*>(ho + o_max) + a, reinterpret_cast<uint32_t*>(ho + o_fit) + a,
                                   reinterpret_cast<uint32_t*>(ho + o_hist) + (size_t)a * KSG_HEADROOM_SLOTS,
@@ -2546,7 +1719,7 @@ int ksg_headroom_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, 
   };
   const auto copies = [&](uint32_t a, uint32_t m, bool last) {
     if (counts)
-      HIPCHK(c, hipMemcpyAsync(counts + (size_t)a * c->N, c->d_hcounts, (size_t)m * c->N * sizeof(uint32_t),
+      HIPCHK(c, hipMemcpyAsync(counts + (size_t)a * c->cl.N, c->d_hcounts, (size_t)m * c->cl.N * sizeof(uint32_t),
                                hipMemcpyDeviceToHost, c->st));
     if (last) HIPCHK(c, hipMemcpyAsync(c->h_dn, ho, ob, hipMemcpyDeviceToHost, c->st));
     return KSG_OK;

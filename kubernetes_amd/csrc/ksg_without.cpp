@@ -56,7 +56,7 @@ int without_tables(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint64_t* 
                    const uint32_t* first_absent, bool peers, bool entry_keys, WithoutTables* tabs) {
   int rc;
   // the list: committed uids, each once (an invalid one leaves the device untouched)
-  const uint32_t N = c->N, ns = c->ext_on ? c->ext.n_scalar : 0;
+  const uint32_t N = c->cl.N, ns = c->ext_on ? c->ext.n_scalar : 0;
   std::vector<Listed> on;
   std::unordered_map<uint64_t, uint32_t> idx_of_seq;  // a listed pod's commit sequence number -> list index
   idx_of_seq.reserve(n_absent);
@@ -84,17 +84,17 @@ int without_tables(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint64_t* 
   }
   std::vector<Conflict> cf;
   for (const auto& kv : held) {
-    const auto kit = c->key_ref.find(kv.first);
-    if (kit != c->key_ref.end() && kit->second == kv.second.held) cf.push_back(kv.second);
+    const auto kit = c->mir.key_ref.find(kv.first);
+    if (kit != c->mir.key_ref.end() && kit->second == kv.second.held) cf.push_back(kv.second);
   }
   std::sort(cf.begin(), cf.end(),
             [](const Conflict& a, const Conflict& b) { return a.node != b.node ? a.node < b.node : a.key < b.key; });
-  const bool aff = peers && (c->dev.preds & KSG_PRED_SERVICEAFFINITY) != 0;  // (else no peer is looked up)
+  const bool aff = peers && (c->cl.dev.preds & KSG_PRED_SERVICEAFFINITY) != 0;  // (else no peer is looked up)
   // one buffer: nd_sum uint64[2 + ns][E], touched uint64[nw], then the uint32 arrays nd_off[N + 1],
   // nd_idx[E], cf_off[N + 1], cf_key[F], cf_min[F], first_absent[n], peer int32[n], and with
   // entry_keys ek_off[E + 1], ek_key[K]
   const size_t E = on.size(), F = cf.size();
-  const size_t o_touch = (2 + (size_t)ns) * E * 8, o_ndoff = o_touch + (size_t)c->nw * 8;
+  const size_t o_touch = (2 + (size_t)ns) * E * 8, o_ndoff = o_touch + (size_t)c->cl.nw * 8;
   const size_t o_ndidx = o_ndoff + ((size_t)N + 1) * 4, o_cfoff = o_ndidx + E * 4, o_cfkey = o_cfoff + ((size_t)N + 1) * 4;
   const size_t o_cfmin = o_cfkey + F * 4, o_fa = o_cfmin + F * 4, o_peer = o_fa + (size_t)n * 4;
   const size_t o_ekoff = o_peer + (size_t)n * 4, o_ekkey = o_ekoff + (entry_keys ? (E + 1) * 4 : 0);
@@ -152,7 +152,7 @@ int without_tables(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint64_t* 
     PeerChain& pc = ins.first->second;
     if (ins.second) {
       uint32_t lowest = UINT32_MAX;
-      for (const auto& m : c->svc_members[s]) {  // seq order: commit order
+      for (const auto& m : c->mir.svc_members[s]) {  // seq order: commit order
         const int32_t code = m.second < N ? (int32_t)m.second : -2;
         const auto it = idx_of_seq.find(m.first);
         if (it == idx_of_seq.end()) {
@@ -206,7 +206,7 @@ int ksg_explain_without(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext,
   if ((rc = query_validate(c, pods, ext, n, ids, n_ids, std::cref(position)))) return rc;
   WithoutTables tabs;
   if ((rc = without_tables(c, pods, n, absent_uids, n_absent, first_absent, true, false, &tabs))) return rc;
-  const uint32_t N = c->N;
+  const uint32_t N = c->cl.N;
   const ksg_pod_ext* dext;
   if ((rc = query_upload(c, pods, ext, n, ids, n_ids, false, &dext))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->d_wtab, c->h_wtab, tabs.bytes, hipMemcpyHostToDevice, c->st));
@@ -225,7 +225,7 @@ int ksg_explain_without(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext,
   const auto launch = [&](uint32_t a, uint32_t m) {
     w.first_absent = d_fa + a;  // (offset like the pods)
     w.peer = d_peer ? d_peer + a : nullptr;
-    HIPCHK(c, ksg_launch_explain_without(c->dev, w, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m,
+    HIPCHK(c, ksg_launch_explain_without(c->cl.dev, w, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m,
                                          codes ? c->d_wcodes.p : nullptr, d_hist + (size_t)a * KSG_EXPLAIN_SLOTS,
                                          d_err + a, c->st));
     return KSG_OK;

@@ -1,5 +1,5 @@
 """The library's host runtime under UBSan on the MI355X: a child pytest process loads
-kubernetes_amd/libkschedgpu_ubsan.so (KSG_LIB; the same gfx950 kernels, ksg_runtime.cpp
+kubernetes_amd/libkschedgpu_ubsan.so (KSG_LIB; the same gfx950 kernels, the host files
 built with -Xarch_host -fsanitize=undefined -fno-sanitize-recover=all by build()) and runs
 the GPU parity, begin/commit, add/remove, queued-update and reflector-thread tests. The
 first undefined operation on the host side (signed overflow in the mirror's int64

@@ -212,21 +212,22 @@ def _ext_struct(arrs, keep):
     return C.byref(e)
 
 
-def _still_old(dev, case, live, before, what):
+def _still_old(dev, case, live, before, what, step=0):
     d = diff_states(engine_state(dev, case.n_scalar), before)
     assert d is None, (what, d)
-    assert dev.n_nodes == case.n_nodes(0)
+    assert dev.n_nodes == case.n_nodes(step)
 
 
-def _old_list_in_force(dev, case, live):
-    """A following small batch is exactly the oracle's on the OLD list (its pods join `live`)."""
-    orc = case.rebuild(OracleScheduler(case.cfg), live, 0)
+def _old_list_in_force(dev, case, live, step=0, lo=uc.FILL + 1):
+    """A following small batch (pool pods [lo, lo + 20)) is exactly the oracle's on the OLD list,
+    list `step` (its pods join `live`)."""
+    orc = case.rebuild(OracleScheduler(case.cfg), live, step)
     try:
-        b = case.slice(0, uc.FILL + 1, uc.FILL + 21)
+        b = case.slice(step, lo, lo + 20)
         got, want = dev.batch(b, 99), orc.batch(b, 99)
         assert np.array_equal(got[0], want[0]) and got[1] == want[1]
-        live += [case.pool_live(0, uc.FILL + 1 + i, int(x)) for i, x in enumerate(got[0]) if x >= 0]
-        _audit(dev, case, live, 0, "batch on the old list")
+        live += [case.pool_live(step, lo + i, int(x)) for i, x in enumerate(got[0]) if x >= 0]
+        _audit(dev, case, live, step, "batch on the old list")
     finally:
         orc.close()
 
@@ -280,6 +281,47 @@ def test_refused_calls_change_nothing():
         live.append(case.pool_live(0, uc.FILL + 30, dev.commit(0)))
         _audit(dev, case, live, 0, "commit after the refused update")
         _old_list_in_force(dev, case, live)
+    finally:
+        dev.close()
+
+
+def test_refused_updated_refused_reset_in_one_context():
+    """One context's node list through every way it changes hands, in a row: a refusal after the
+    new list's parts were being built ("shard size": the old parts come back), the same update with
+    good arguments (the old parts go), a second such refusal on the new list, then ksg_set_cluster
+    of the original list with the pods added again. After each step the device state is the
+    model's and a 20-pod batch the oracle's."""
+    import copy
+
+    case = uc.UpdateCase("shrink")
+    dev = DeviceScheduler(case.cfg, device=0)
+    try:
+        dev.set_window(128)
+        case.load(dev)
+        live, _ = case.fill(dev)
+        o2n, out = case.maps(0)
+        oo, on = [a for a, _ in out], [b for _, b in out]
+        huge = copy.copy(case.arrays[1])  # one node more than a shard holds, no labels
+        huge.nodes = np.zeros(128 * 1024 + 1, abi.NODE_DTYPE)
+        before = engine_state(dev, 0)
+        assert _raw(dev, huge, o2n, oo, on) == abi.KSG_ERR_CAPACITY
+        _still_old(dev, case, live, before, "shard size, list 0")
+        _old_list_in_force(dev, case, live)
+        _update(dev, case, 0)
+        _audit(dev, case, live, 1, "update")
+        _old_list_in_force(dev, case, live, 1, uc.FILL + 21)
+        # the way back to list 0, by names, with the oversized node array again
+        back = np.asarray([case.host_id(0, nm) for nm in case.names[1]], np.uint32)
+        outside = [nm for nm in list(case.it.ext_hosts) if nm not in case.ranks[1]]
+        assert any(l.host in outside for l in live), "a pod is on a host outside list 1"
+        before = engine_state(dev, 0)
+        assert _raw(dev, huge, back, [case.host_id(1, nm) for nm in outside],
+                    [case.host_id(0, nm) for nm in outside]) == abi.KSG_ERR_CAPACITY
+        _still_old(dev, case, live, before, "shard size, list 1", 1)
+        _old_list_in_force(dev, case, live, 1, uc.FILL + 41)
+        case.rebuild(dev, live, 0)
+        _audit(dev, case, live, 0, "set_cluster of list 0 and the pods again")
+        _old_list_in_force(dev, case, live, 0, uc.FILL + 61)
     finally:
         dev.close()
 

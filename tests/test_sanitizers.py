@@ -4,7 +4,7 @@
   operation aborts; signed overflow matters because the reference's Go int64
   arithmetic wraps and the C must do it unsigned) and under ASan (LD_PRELOAD of gcc's
   runtime), through the golden-vector, engine and cross-check suites.
-* The library's host runtime (kubernetes_amd/csrc/ksg_runtime.cpp) built with
+* The library's host runtime (kubernetes_amd/csrc/*.cpp) built with
   `-Xarch_host -fsanitize=undefined` into libkschedgpu_ubsan.so (GPU code unchanged),
   loaded through KSG_LIB by the -m gpu run in tests/test_gpu_ubsan_runtime.py.
 """

@@ -16,7 +16,7 @@ mkdir -p "$C/_obj"
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-strict-aliasing -Wall -Wno-unused-function"
 pids=""; objs=""
 for s in "$C"/ksg_*.hip "$C"/*.cpp; do
-  o=$C/_obj/$(basename "${s%.*}").o
+  o=$C/_obj/$(basename "$s").o  # (with the extension: ksg_preempt.hip and ksg_preempt.cpp are two objects)
   X=""
   case "$s" in */ksg_plain_large.hip) X="-mllvm -amdgpu-sched-strategy=max-ilp";; esac
   hipcc $F $X -c "$s" -o "$o" & pids="$pids $!"
