@@ -114,6 +114,9 @@
 // flags and first peers in commit order), 5.. producers: 12 waves (7 producers), 8 at P = 32,
 // where a producer's T0 copy needs the registers of two waves per SIMD
 __host__ __device__ constexpr uint32_t pl_nt(int P) { return P >= 32 ? 512u : 768u; }
+// ring entries: an entry holds T0 (8 B) and its in-row prefixes (2 B) per word, so larger shards
+// keep a shorter ring
+__host__ __device__ constexpr uint32_t pl_ring(uint32_t P) { return P <= 8 ? 16u : P == 16 ? 8u : 5u; }
 #define KSG_PL_FW KSG_RES_P0
 #define KSG_PL_P0 (KSG_PL_FW + 1)
 // the resolver's ring holds the d1 bitmaps up to P = 4 (16,384 nodes)
@@ -166,7 +169,7 @@ struct PlLdsOff {
 
 __host__ __device__ inline PlLdsOff plain_lds_offsets(uint32_t P, uint32_t nflag, uint32_t W) {
   PlLdsOff o;
-  const uint32_t R = win2_ring(P, false);
+  const uint32_t R = pl_ring(P);
   uint32_t at = 0;
   o.ctl = at;     at += win_al16(sizeof(PlCtl));
   o.r_hdr = at;   at += win_al16((size_t)R * sizeof(RingHdr));
@@ -461,7 +464,7 @@ __device__ __forceinline__ void win_plain_body(const KsgDev d, uint32_t wcap, Ks
   const uint32_t lane = tid & 63;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t nflag = (d.n_services + 31) / 32;
-  constexpr uint32_t RING = win2_ring(P, false);
+  constexpr uint32_t RING = pl_ring(P);
   constexpr uint32_t NT = pl_nt(P);
   constexpr uint32_t NPW = NT / 64 - KSG_PL_P0;  // producer waves
   const uint32_t f_nwg = FUSED ? (d.nwords + NT / 64 - 1) / (NT / 64) : 0u;  // (fused: word groups per pod group)

@@ -1,8 +1,9 @@
 // ksg_resolver.h — pieces shared by the window path's in-order resolvers
 // (phase B): the resolver record's dword offsets, the ring and slot records,
 // the LDS polling primitives, the drop tests against a committed node, and the
-// select helpers. Included by ksg_window.hip (phase A, the anti-affinity
-// resolvers) and ksg_plain.hip (the resolver of every other configuration).
+// select helper. Included by ksg_window.hip (phase A's launch, the two
+// ServiceAntiAffinity resolvers), ksg_plain.hip (the resolver of every other
+// configuration) and ksg_score.h (phase A's per-wave body).
 #pragma once
 #include "ksg_device.h"
 
@@ -26,18 +27,13 @@
 
 // threads of the resolver workgroup: 8 waves
 // (16 waves for P <= 8 measured no faster than 8: the chain, not the producers, limits)
-__host__ __device__ constexpr uint32_t win_res_nt(uint32_t P) { return P <= 8 ? 512u : 512u; }
+#define KSG_RES_NT 512u
 #define KSG_RES_C0 2                                  // first checker wave (0: committer, 1: scribe)
 #define KSG_RES_NCHK 2                                // checker waves
 #define KSG_RES_P0 (KSG_RES_C0 + KSG_RES_NCHK)        // first producer wave
-#define KSG_RES_NPW (KSG_RES_NT / 64 - KSG_RES_P0)    // producer waves (KSG_RES_NT: in the kernel)
+#define KSG_RES_NPW (KSG_RES_NT / 64 - KSG_RES_P0)    // producer waves
 // ring entries: 16, or 4 when the T0 words of an entry are large (P > 8: more than 32k nodes)
 __host__ __device__ constexpr uint32_t win_ring(uint32_t P) { return P <= 8 ? 16u : 4u; }
-// the register-slot resolver without ServiceAntiAffinity: an entry holds T0 (8 B)
-// and its in-row prefixes (2 B) per word, so larger shards keep a longer ring
-__host__ __device__ constexpr uint32_t win2_ring(uint32_t P, bool anti) {
-  return anti || P <= 8 ? win_ring(P) : P == 16 ? 8u : 5u;
-}
 // Shards past 32k nodes (P > 8): the re-rank's per-domain node bitmaps (one P * 512 B bitmap per
 // domain row) are read from their HBM copy (x.zmap, L2-resident: rows x words x 8 B) instead of
 // LDS; past 64k nodes (P > 16) the pod's fit-at-the-snapshot and best-per-row (B) bitmaps are
@@ -141,8 +137,8 @@ __host__ __device__ constexpr uint32_t win_peer_cap(uint32_t nflag, uint32_t W) 
   return nflag * 32u < W * (uint32_t)KSG_SLOT_SVCS ? nflag * 32u : W * (uint32_t)KSG_SLOT_SVCS;
 }
 
-__host__ __device__ inline WinLdsOff win_lds_offsets(uint32_t P, uint32_t nflag, uint32_t W, bool anti,
-                                                     uint32_t dz = 0, uint32_t nsvc = 0) {
+__host__ __device__ inline WinLdsOff win_lds_offsets(uint32_t P, uint32_t nflag, uint32_t W, uint32_t dz = 0,
+                                                     uint32_t nsvc = 0) {
   WinLdsOff o;
   const uint32_t KSG_RING = win_ring(P);
   uint32_t at = 0;
@@ -152,8 +148,8 @@ __host__ __device__ inline WinLdsOff win_lds_offsets(uint32_t P, uint32_t nflag,
   o.r_rec = at;   at += win_al16((size_t)KSG_RING * KSG_WIN_SUM_DWORDS * 4);
   o.r_mod = at;   at += win_al16((size_t)KSG_RING * 64 * 4);
   o.r_svc = at;   at += win_al16((size_t)KSG_RING * sizeof(RingSvc));
-  // fit bitmaps (anti-affinity; past 64k nodes read from phase A's rows instead, win2_fg)
-  o.r_fit = at;   at += anti && !win2_fg(P) ? win_al16((size_t)KSG_RING * P * 64 * 8) : 0u;
+  // fit bitmaps (past 64k nodes read from phase A's rows instead, win2_fg)
+  o.r_fit = at;   at += !win2_fg(P) ? win_al16((size_t)KSG_RING * P * 64 * 8) : 0u;
   o.s_meta = at;  at += win_al16((size_t)KSG_MAX_SLOTS * sizeof(SlotMeta));
   o.s_cap = at;   at += win_al16((size_t)KSG_MAX_SLOTS * sizeof(I64x2));
   o.s_snp = at;   at += win_al16((size_t)KSG_MAX_SLOTS * sizeof(I64x2));
@@ -265,34 +261,6 @@ __device__ __forceinline__ uint32_t select_in_lanes(const uint64_t (&bits)[P], u
       __builtin_amdgcn_mbcnt_hi((uint32_t)(wsel >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wsel, 0u));
   const uint32_t bsel = (uint32_t)__builtin_ctzll(__ballot(((wsel >> lane) & 1ULL) && rank == local));
   return ((uint32_t)ol * P + qsel) * 64 + bsel;
-}
-
-// The same for a q-major bitmap (lane l holds words q*64 + l): given each
-// lane's bits below it in row q (ex[q]) and the bits below each row (rowex,
-// wave-uniform, ascending), the target-th set bit (ascending) as a bit offset.
-template <int P>
-__device__ __forceinline__ uint32_t select_qmajor(const uint64_t (&bits)[P], const uint32_t (&ex)[P],
-                                                  const uint32_t (&rowex)[P], uint32_t target, uint32_t lane) {
-  uint32_t qs = 0;
-#pragma unroll
-  for (int q = 1; q < P; ++q)
-    if (rowex[q] <= target) qs = q;  // (an empty row has the next row's prefix)
-  uint64_t w = 0;
-  uint32_t e = 0, rb = 0;
-#pragma unroll
-  for (int q = 0; q < P; ++q)
-    if ((uint32_t)q == qs) {
-      w = bits[q];
-      e = ex[q];
-      rb = rowex[q];
-    }
-  const uint32_t loc = target - rb;
-  const uint32_t ls = (uint32_t)__builtin_ctzll(__ballot(e <= loc && loc < e + (uint32_t)__popcll(w)));
-  const uint64_t ws = readlane64(w, (int)ls);
-  const uint32_t lw = loc - (uint32_t)__builtin_amdgcn_readlane((int)e, (int)ls);
-  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(ws >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ws, 0u));
-  const uint32_t bsel = (uint32_t)__builtin_ctzll(__ballot(((ws >> lane) & 1ULL) && rank == lw));
-  return (qs * 64 + ls) * 64 + bsel;
 }
 
 // LDS views of the slots (structure of arrays by slot index)

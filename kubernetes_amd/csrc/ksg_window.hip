@@ -157,10 +157,8 @@ __global__ __launch_bounds__(KSG_SC_NT) KSG_PA_ATTR void ksg_win_score_kernel(Ks
 // (tests/test_gpu_fuzz.py runs each skew once against the oracle).
 // The node state in HBM stays the pristine snapshot while the window
 // resolves; the window's deltas are written back once, at the end.
-// ANTI: ServiceAntiAffinity is on (its checks are compiled only into these
-// instantiations: they cost the others scalar registers on the chain)
-template <int P, bool STAMP, bool ANTI>
-__global__ __launch_bounds__(win_res_nt(P)) void ksg_win_resolve_kernel(KsgDev d, uint32_t wcap, KsgWinRun* run,
+template <int P, bool STAMP>
+__global__ __launch_bounds__(KSG_RES_NT) void ksg_win_resolve_kernel(KsgDev d, uint32_t wcap, KsgWinRun* run,
                                                                     const KsgWinSum* __restrict__ sums,
                                                                     const KsgWinXchg x, uint64_t* rng_io,
                                                                     int32_t* __restrict__ out_batch) {
@@ -175,18 +173,15 @@ __global__ __launch_bounds__(win_res_nt(P)) void ksg_win_resolve_kernel(KsgDev d
   const uint32_t nflag = (d.n_services + 31) / 32;
   const uint32_t nwords = d.nwords;
   constexpr uint32_t KSG_RING = win_ring(P);
-  constexpr uint32_t KSG_RES_NT = win_res_nt(P);
   // re-rank: a pod whose service had commits earlier in the window is ranked
   // again per domain row (committer) instead of ending the window
-  const bool rr = ANTI && x.rr != 0;
+  const bool rr = x.rr != 0;
   const uint32_t dz = rr ? x.dz : 0u;
-  if constexpr (ANTI) {  // this window's score pass has read the domain counts: zero them for the next
-    // (with the re-rank the producers stage them: the committer zeroes them at the end)
-    if (!rr)
-      for (uint32_t t = tid; t < x.dcnt_n; t += KSG_RES_NT) x.dcnt[t] = 0;
-  }
-  constexpr bool anti_on = ANTI;  // (the host passes fit bitmaps, x.fit_off != 0, exactly then)
-  const WinLdsOff o = win_lds_offsets(P, nflag, wcap, anti_on, dz, d.n_services);
+  // this window's score pass has read the domain counts: zero them for the next
+  // (with the re-rank the producers stage them: the committer zeroes them at the end)
+  if (!rr)
+    for (uint32_t t = tid; t < x.dcnt_n; t += KSG_RES_NT) x.dcnt[t] = 0;
+  const WinLdsOff o = win_lds_offsets(P, nflag, wcap, dz, d.n_services);
   uint64_t* const r_b = reinterpret_cast<uint64_t*>(smem + o.r_b);   // [ring][P*64] best-per-row words
   int32_t* const r_mb = reinterpret_cast<int32_t*>(smem + o.r_mb);   // [ring][KSG_RR_MAXZ] best per row
   int32_t* const r_dc = reinterpret_cast<int32_t*>(smem + o.r_dc);   // [ring][KSG_RR_MAXZ] domain counts
@@ -379,22 +374,20 @@ __global__ __launch_bounds__(win_res_nt(P)) void ksg_win_resolve_kernel(KsgDev d
       if (lane < KSG_WIN_SUM_DWORDS) r_rec[e * KSG_WIN_SUM_DWORDS + lane] = rec;
 #pragma unroll
       for (int q = 0; q < P; ++q) r_t0[(size_t)e * P * 64 + lane * P + q] = t0[q];
-      if (anti_on) {
-        if constexpr (!win2_fg(P))
+      if constexpr (!win2_fg(P))
 #pragma unroll
-          for (int q = 0; q < P; ++q)
-            r_fit[(size_t)e * P * 64 + lane * P + q] =
-                wb_at[q] != ~0u ? *reinterpret_cast<const uint64_t*>(x.buf + wb_at[q] + x.fit_off + j * row_b) : 0ULL;
-        if (rr) {  // the re-rank's inputs: best-per-row words, best per row, domain counts
+        for (int q = 0; q < P; ++q)
+          r_fit[(size_t)e * P * 64 + lane * P + q] =
+              wb_at[q] != ~0u ? *reinterpret_cast<const uint64_t*>(x.buf + wb_at[q] + x.fit_off + j * row_b) : 0ULL;
+      if (rr) {  // the re-rank's inputs: best-per-row words, best per row, domain counts
 #pragma unroll
-          for (int q = 0; q < P; ++q)
-            r_b[(size_t)e * P * 64 + lane * P + q] =
-                wb_at[q] != ~0u ? *reinterpret_cast<const uint64_t*>(x.buf + wb_at[q] + x.b_off + j * row_b) : 0ULL;
-          if (lane < dz) {
-            r_mb[e * KSG_RR_MAXZ + lane] = x.dmb[(size_t)j * dz + lane];
-            r_dc[e * KSG_RR_MAXZ + lane] =
-                lane + 1 < dz ? x.dcnt[(size_t)j * d.n_domains_total + d.anti_dom_off[0] + lane] : 0;
-          }
+        for (int q = 0; q < P; ++q)
+          r_b[(size_t)e * P * 64 + lane * P + q] =
+              wb_at[q] != ~0u ? *reinterpret_cast<const uint64_t*>(x.buf + wb_at[q] + x.b_off + j * row_b) : 0ULL;
+        if (lane < dz) {
+          r_mb[e * KSG_RR_MAXZ + lane] = x.dmb[(size_t)j * dz + lane];
+          r_dc[e * KSG_RR_MAXZ + lane] =
+              lane + 1 < dz ? x.dcnt[(size_t)j * d.n_domains_total + d.anti_dom_off[0] + lane] : 0;
         }
       }
       if (inl && lane < n_svcs) {
@@ -460,7 +453,7 @@ __global__ __launch_bounds__(win_res_nt(P)) void ksg_win_resolve_kernel(KsgDev d
                        1ULL << (nd & 63));
             t0_drop = drop && in_t0;
           }
-          const bool fit_snap = anti_on && pv.s >= 0 && ((fit_word(e, i, nd >> 6) >> (nd & 63)) & 1ULL);
+          const bool fit_snap = pv.s >= 0 &&((fit_word(e, i, nd >> 6) >> (nd & 63)) & 1ULL);
           bool fits_now = false;
           if (fit_snap) {
             fits_now = slot_fits_now(S, sl, pv, rec, res_on, ports_on, disk_on);
@@ -583,7 +576,7 @@ __global__ __launch_bounds__(win_res_nt(P)) void ksg_win_resolve_kernel(KsgDev d
             changed = aff_on && peer == -1 && !((L_peerset[my_sv >> 5] >> (my_sv & 31)) & 1u);
             // ServiceAntiAffinity divides by the service's pod count: any commit changes it
             // (the re-rank takes that: later pods of the service are ranked again)
-            changed |= anti_on && !rr;
+            changed |= !rr;
             if (rr) atomicAdd(&L_nsv[my_sv], 1u);
           }
           // first commit of a service with no peer yet: record the peer (in order)
@@ -710,7 +703,7 @@ __global__ __launch_bounds__(win_res_nt(P)) void ksg_win_resolve_kernel(KsgDev d
     const uint32_t k0 = __builtin_amdgcn_readfirstlane(r_hdr[e].k0);
     const int32_t s = (int32_t)__builtin_amdgcn_readlane(rec, WS_SVC);
     uint32_t mv_n = 0;  // (re-rank) earlier window commits of the pod's service
-    if (s >= 0 && (spread_on || aff_on || anti_on)) {
+    if (s >= 0) {
       // the flags of every earlier commit that may concern this pod's service
       const bool prev_has = __ballot(lane < prev_nsv && prev_sv == (uint32_t)s) != 0;
       if (!wait_scribe(prev_has ? i : (i ? i - 1 : 0))) {
@@ -834,7 +827,7 @@ __global__ __launch_bounds__(win_res_nt(P)) void ksg_win_resolve_kernel(KsgDev d
       chk_stop |= __builtin_amdgcn_readfirstlane(ctl->chk_stop[c][par]);
     }
     bool ls_counts = false;  // (re-rank) the last slot's node is still among the pod's filtered nodes
-    if (anti_on && pv.s >= 0 && !chk_stop && ls_valid &&
+    if (pv.s >= 0 && !chk_stop && ls_valid &&
         ((fit_word(e, i, ls_node >> 6) >> (ls_node & 63)) & 1ULL)) {
       // the last slot, from the register copy: does the pod still fit it?
       const int64_t now_c = (int64_t)((uint64_t)ls_snp_c + (uint64_t)ls_dl_c);
@@ -1161,30 +1154,40 @@ __global__ __launch_bounds__(win_res_nt(P)) void ksg_win_resolve_kernel(KsgDev d
 }
 
 // ---------------------------------------------------------------------------
-// phase B, register-slot resolver (every configuration without
-// ServiceAntiAffinity; that one keeps the resolver above)
+// phase B, register-slot resolver: ServiceAntiAffinity with the per-domain
+// re-rank (x.rr; the LDS-slot resolver above takes every other
+// ServiceAntiAffinity configuration, ksg_plain.hip every configuration without)
 // ---------------------------------------------------------------------------
 // The window's committed nodes ("slots", at most 128) are owned by two checker
 // waves, one slot per lane: the node's capacity, snapshot and window delta of
-// the requested totals and 10/capacity live in the owner lane's registers; the
-// conflict keys and service entries the window added live in an LDS table by
-// slot (keys and service ids written by the committer at the commit, the
-// services' snapshot counts by the owner checker).
-//  CHECKERS run a pod ahead of the committer: for pod i they apply commit i-2
-//    (a new slot takes the node's snapshot from the producer's staging when it
-//    is the predicted node, else from L2; the service flags and first peers
-//    later pods stop on are set here) and test pod i against every slot as of
-//    commits <= i-2.
-//  COMMITTER (wave 0) re-checks only the slot commit i-1 went into (its window
-//    delta in registers, its lists from the table, the node's snapshot loaded at
-//    the top of the iteration), adds the checkers' drops (a commit can only
-//    make a node worse, so drops as of i-2 stay drops), selects the ix-th live
-//    tie (the staged prediction when nothing dropped), writes the pod's lists
-//    into the table and publishes the commit record.
-//  PRODUCERS stage pods ahead into the ring. The draw index of pod j is the
-//    number of drawable pods before j, read from two LDS bitmaps every producer
-//    fills as soon as it knows its pod's max score (no producer-to-producer
-//    hand-off chain).
+// the requested totals, 10/capacity and domain row live in the owner lane's
+// registers; the conflict keys and service entries the window added live in an
+// LDS table by slot (keys and service ids written by the committer at the
+// commit, the services' snapshot counts by the owner checker).
+//  PRODUCERS (waves 4..7) stage pods ahead into the ring, lane l holding words
+//    l*P + q of every bitmap: T0, the fit-at-the-snapshot and best-per-row (B)
+//    nodes, the row bests, the domain counts and the B nodes per row. The draw
+//    index of pod j is the number of drawable pods before j, read from two LDS
+//    bitmaps every producer fills as soon as it knows its pod's max score (no
+//    producer-to-producer hand-off chain).
+//  CHECKERS (waves 2..3) run a pod ahead of the committer: for pod i they apply
+//    commit i-2 (a new slot takes the node's snapshot from the producer's
+//    staging when it is the predicted node, else from L2) and test pod i against
+//    every slot as of commits <= i-2: a B node that got worse is scattered into
+//    the drop bitmap (those in T0 are counted) and counted in its domain row; a
+//    slot the pod still fits adds the window's commits of the pod's service to
+//    its row's count; one it no longer fits that held the service's pods ends
+//    the window (the domain counts moved).
+//  X-CHECKER (wave 1) does the same for pod i against the slot commit i-1 went
+//    into, as of that commit, from the drawn node alone (it replays the
+//    committer's slot bookkeeping), then sets the service flags and first peers
+//    of commit i-1, in commit order.
+//  COMMITTER (wave 0) adds the checkers' drops and the x-checker's verdict (a
+//    commit can only make a node worse, so drops as of i-2 stay drops). A pod
+//    whose service had commits earlier in the window is re-ranked per domain
+//    row; any other takes the staged prediction when nothing dropped, else the
+//    ix-th live tie of T0 minus the drop bitmap. It posts the drawn node, writes
+//    the pod's lists into the table and publishes the commit record.
 // one per window pod; the first 16 bytes are the commit record (one 16-byte store),
 // then the pod's answer and its drawn node (written apart)
 struct alignas(16) WinCommit {
@@ -1204,9 +1207,7 @@ struct alignas(16) WinCtl2 {
   uint32_t n_peer;    // first service peers recorded in the window (L_peer entries)
   uint32_t chk_seq[KSG_RES_NCHK];     // pods checker c is done with
   uint32_t chk_cnt[KSG_RES_NCHK][2];  // checker c's drops for the pod of parity p
-  // (no ServiceAntiAffinity) checker c's dropping slots for the pod of parity p
-  // (lane l: slot 64c + l; its drop's ascending T0 position is in L_dpos)
-  uint32_t chk_msk[KSG_RES_NCHK][2][2];
+  uint32_t chk_msk[KSG_RES_NCHK][2][2];  // (nothing reads or writes it: kept so the fields behind it stay put)
   uint32_t fin[KSG_RES_NCHK];         // checker c applied every commit and wrote its slots back
   uint32_t hang;                      // a wait exceeded its spin limit (a bug)
   uint32_t xseq;                      // pods the x-checker is done with
@@ -1231,24 +1232,20 @@ struct alignas(16) WinCtl2 {
 };
 
 struct WinLdsOff2 {
-  // r_lp: per ring entry and lane, the T0 bits in lanes below / up to it
-  // (exclusive, inclusive prefix); r_wp: per ring entry and word, the T0 bits
-  // in the lane's words below it (u16); dpos: the checkers' drop positions in
-  // T0 by pod parity and slot (no ServiceAntiAffinity: the sparse select)
-  uint32_t r_lp, r_wp, dpos;
   uint32_t ctl, r_hdr, r_t0, r_rec, r_mod, r_svc;
   uint32_t cm, peer, flag, peerset, drop, pub, drw, clist;
-  // ServiceAntiAffinity re-rank (dz > 0; see the LDS-slot resolver's WinLdsOff)
+  // the re-rank's arrays (see the LDS-slot resolver's WinLdsOff)
   uint32_t r_fit, r_b, r_mb, r_dc, zm, nsv, dca, r_kz, ddr;
   uint32_t total;
 };
 
-
-// (rr: the re-rank's arrays; -1: iff dz > 0; the kernel passes a constant)
-__host__ __device__ inline WinLdsOff2 win2_lds_offsets(uint32_t P, uint32_t nflag, uint32_t W, uint32_t dz = 0,
-                                                       uint32_t nsvc = 0, int rr_ = -1) {
+__host__ __device__ inline WinLdsOff2 win2_lds_offsets(uint32_t P, uint32_t nflag, uint32_t W, uint32_t dz,
+                                                       uint32_t nsvc) {
   WinLdsOff2 o;
-  const uint32_t R = win2_ring(P, dz != 0);
+  // (every caller passes dz != 0, which the compiler cannot know: with the test folded away the
+  // offsets behind the ring become constants in the P > 8 kernels and their device code changes,
+  // so it stays until that change is measured; 8 and 5 are never taken)
+  const uint32_t R = dz != 0 || P <= 8 ? win_ring(P) : P == 16 ? 8u : 5u;
   uint32_t at = 0;
   o.ctl = at;     at += win_al16(sizeof(WinCtl2));
   o.r_hdr = at;   at += win_al16((size_t)R * sizeof(RingHdr));
@@ -1256,22 +1253,18 @@ __host__ __device__ inline WinLdsOff2 win2_lds_offsets(uint32_t P, uint32_t nfla
   o.r_rec = at;   at += win_al16((size_t)R * KSG_WIN_SUM_DWORDS * 4);
   o.r_mod = at;   at += win_al16((size_t)R * 64 * 4);
   o.r_svc = at;   at += win_al16((size_t)R * sizeof(RingSvc));
-  // fixed sizes first (given P and whether the re-rank runs): their offsets are
-  // compile-time constants in the kernel, not registers the roles' loops keep
-  const bool rr = rr_ < 0 ? dz != 0 : rr_ != 0;
+  // fixed sizes first (given P): their offsets are compile-time constants in
+  // the kernel, not registers the roles' loops keep
   o.clist = at;   at += win_al16((size_t)KSG_MAX_SLOTS * KSG_CL_W * 4);
-  o.drop = at;    at += rr ? win_al16((size_t)2 * P * 64 * 8) : 0u;  // (the re-rank's drop bitmap)
+  o.drop = at;    at += win_al16((size_t)2 * P * 64 * 8);  // (the re-rank's drop bitmap)
   // (P > 16: the fit and B bitmaps are read from phase A's output instead, win2_fg)
-  o.r_fit = at;   at += rr && !win2_fg(P) ? win_al16((size_t)R * P * 64 * 8) : 0u;
-  o.r_b = at;     at += rr && !win2_fg(P) ? win_al16((size_t)R * P * 64 * 8) : 0u;
-  o.r_mb = at;    at += rr ? win_al16((size_t)R * KSG_RR_MAXZ * 4) : 0u;
-  o.r_dc = at;    at += rr ? win_al16((size_t)R * KSG_RR_MAXZ * 4) : 0u;
-  o.dca = at;     at += rr ? win_al16((size_t)KSG_RES_NCHK * 2 * KSG_RR_MAXZ * 4) : 0u;
-  o.r_kz = at;    at += rr ? win_al16((size_t)R * KSG_RR_MAXZ * 4) : 0u;
-  o.ddr = at;     at += rr ? win_al16((size_t)KSG_RES_NCHK * 2 * KSG_RR_MAXZ * 4) : 0u;
-  o.r_lp = at;    at += rr ? 0u : win_al16((size_t)R * 64 * 8);
-  o.r_wp = at;    at += rr ? 0u : win_al16((size_t)R * P * 64 * 2);
-  o.dpos = at;    at += rr ? 0u : win_al16((size_t)2 * KSG_MAX_SLOTS * 4);
+  o.r_fit = at;   at += !win2_fg(P) ? win_al16((size_t)R * P * 64 * 8) : 0u;
+  o.r_b = at;     at += !win2_fg(P) ? win_al16((size_t)R * P * 64 * 8) : 0u;
+  o.r_mb = at;    at += win_al16((size_t)R * KSG_RR_MAXZ * 4);
+  o.r_dc = at;    at += win_al16((size_t)R * KSG_RR_MAXZ * 4);
+  o.dca = at;     at += win_al16((size_t)KSG_RES_NCHK * 2 * KSG_RR_MAXZ * 4);
+  o.r_kz = at;    at += win_al16((size_t)R * KSG_RR_MAXZ * 4);
+  o.ddr = at;     at += win_al16((size_t)KSG_RES_NCHK * 2 * KSG_RR_MAXZ * 4);
   o.cm = at;      at += win_al16((size_t)W * sizeof(WinCommit));
   o.peer = at;    at += win_al16((size_t)win_peer_cap(nflag, W) * 2 * 4);
   o.pub = at;     at += win_al16((size_t)((W + 31) / 32) * 4);
@@ -1279,21 +1272,17 @@ __host__ __device__ inline WinLdsOff2 win2_lds_offsets(uint32_t P, uint32_t nfla
   o.flag = at;    at += win_al16((size_t)nflag * 4);
   o.peerset = at; at += win_al16((size_t)nflag * 4);
   o.zm = at;      at += win2_zg(P) ? 0u : win_al16((size_t)dz * P * 64 * 8);  // (P > 8: from HBM, win2_zg)
-  o.nsv = at;     at += rr ? win_al16((size_t)nsvc * 4) : 0u;
+  o.nsv = at;     at += win_al16((size_t)nsvc * 4);
   o.total = at;
   return o;
 }
 
-
-// ANTI: ServiceAntiAffinity with the re-rank (x.rr; the LDS-slot resolver above
-// takes every other anti-affinity configuration)
-//
 // Hand-offs (LDS; every poll is relaxed loads then one LDS-only acquire fence,
 // every post a workgroup-scope release store after the data it covers):
 //
 //   flag / data              writer      reader              pod index        ordered by
 //   r_hdr[e].ready + entry   producer j  all but producers   j                ready = j+1 release after the entry
-//    (record, T0, fit, B,                                                     (lane prefixes r_lp / r_wp too)
+//    (record, T0, fit, B,
 //    row bests / counts)
 //   L_pub / L_drw bits       producer j  producers > j       j                L_drw before L_pub (atomicOr, in order)
 //   L_cm[i].xn               committer   x-checker           i (checks i+1)   xn_seq = i+1 release after it
@@ -1302,8 +1291,8 @@ __host__ __device__ inline WinLdsOff2 win2_lds_offsets(uint32_t P, uint32_t nfla
 //   slot row counts          checker     checkers,           commits <= i-2   chk_seq release (the x-checker
 //                            (apply)     x-checker                            reads rows of commits it replayed)
 //   chk_seq[c], chk_cnt,     checker c   committer,          i                chk_seq[c] = i+1 release after the
-//    chk_msk, L_dpos,                    producers                            masks, counts, positions and the
-//    chk_stop, L_dca, L_ddr                                                   anti-affinity row sums
+//    chk_stop, L_drop[i & 1],            producers                            counts, the drop bits (atomicOr) and
+//    L_dca, L_ddr                                                             the anti-affinity row sums
 //   xres, xdz, xdc, xrw,     x-checker   committer           i                xseq = i+1 release after them
 //    xnsv [i & 1]
 //   L_flag, L_peer,          x-checker   committer           commits <= i-2   program order in the x-checker,
@@ -1318,8 +1307,8 @@ __host__ __device__ inline WinLdsOff2 win2_lds_offsets(uint32_t P, uint32_t nfla
 // limit; a timed-out wait sets ctl->hang and the host fails the batch. KSG_DEBUG
 // bits 16..19 add a fixed delay per pod to the committer, x-checker, checkers or
 // producers (tests/test_gpu_fuzz.py runs each skew once against the oracle).
-template <int P, bool STAMP, bool ANTI>
-__global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_t wcap, KsgWinRun* run,
+template <int P, bool STAMP>
+__global__ __launch_bounds__(KSG_RES_NT) void ksg_win_resolve2_kernel(KsgDev d, uint32_t wcap, KsgWinRun* run,
                                                                const KsgWinSum* __restrict__ sums,
                                                                const KsgWinXchg x, uint64_t* rng_io,
                                                                int32_t* __restrict__ out_batch) {
@@ -1333,12 +1322,12 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t nflag = (d.n_services + 31) / 32;
   const uint32_t nwords = d.nwords;
-  constexpr uint32_t RING = win2_ring(P, ANTI);
-  constexpr uint32_t NT = 512;
-  constexpr uint32_t NPW = NT / 64 - KSG_RES_P0;  // producer waves
+  constexpr uint32_t RING = win_ring(P);
+  constexpr uint32_t NT = KSG_RES_NT;
+  constexpr uint32_t NPW = KSG_RES_NPW;
   constexpr uint32_t DW = KSG_WIN_SUM_DWORDS;
-  const uint32_t dz = ANTI ? x.dz : 0u;
-  const WinLdsOff2 o = win2_lds_offsets(P, nflag, wcap, dz, d.n_services, ANTI ? 1 : 0);
+  const uint32_t dz = x.dz;
+  const WinLdsOff2 o = win2_lds_offsets(P, nflag, wcap, dz, d.n_services);
   uint64_t* const r_fit = reinterpret_cast<uint64_t*>(smem + o.r_fit);  // [ring][P*64] fit at the snapshot
   uint64_t* const r_b = reinterpret_cast<uint64_t*>(smem + o.r_b);      // [ring][P*64] best-per-row nodes
   int32_t* const r_mb = reinterpret_cast<int32_t*>(smem + o.r_mb);      // [ring][KSG_RR_MAXZ] best per row
@@ -1365,9 +1354,6 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
   uint32_t* L_pub = reinterpret_cast<uint32_t*>(smem + o.pub);    // pods whose drawable bit is known
   uint32_t* L_drw = reinterpret_cast<uint32_t*>(smem + o.drw);    // drawable pods
   uint32_t* L_cl = reinterpret_cast<uint32_t*>(smem + o.clist);   // [slot][KSG_CL_W]
-  uint32_t* r_lp = reinterpret_cast<uint32_t*>(smem + o.r_lp);    // [ring][64][2] lane prefix (excl, incl)
-  uint16_t* r_wp = reinterpret_cast<uint16_t*>(smem + o.r_wp);    // [ring][P*64] prefix within the lane
-  uint32_t* L_dpos = reinterpret_cast<uint32_t*>(smem + o.dpos);  // [2][KSG_MAX_SLOTS] drop positions
   const bool spread_on = d.w_spread != 0;
   const bool aff_on = (d.preds & KSG_PRED_SERVICEAFFINITY) && d.n_aff > 0;
   const bool res_on = (d.preds & KSG_PRED_PODFITSRESOURCES) != 0;
@@ -1382,7 +1368,7 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
   // from HBM: word w of domain row r (x.zmap), word w of window pod j's phase-A row at byte offset
   // off (x.fit_off, x.b_off; the re-rank runs on one rank, so word w sits at w * 8); words past
   // the shard read 0, as their LDS copies do
-  constexpr bool ZG = ANTI && win2_zg(P), FG = ANTI && win2_fg(P);
+  constexpr bool ZG = win2_zg(P), FG = win2_fg(P);
   auto zm_word = [&](uint32_t r, uint32_t w) -> uint64_t {
     if constexpr (ZG) return w < nwords ? gld(x.zmap + (size_t)r * d.nw + d.wlo + w) : 0ULL;
     else return L_zm[(size_t)r * P * 64 + w];
@@ -1402,16 +1388,13 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
     L_pub[w] = 0;
     L_drw[w] = 0;
   }
-  if constexpr (ANTI)
-    for (uint32_t w = tid; w < 2 * P * 64u; w += NT) L_drop[w] = 0;
-  if constexpr (ANTI) {
-    if constexpr (!ZG)
-      for (uint32_t t = tid; t < dz * P * 64; t += NT) {
-        const uint32_t row = t / (P * 64), w = t % (P * 64);
-        L_zm[t] = w < nwords ? x.zmap[(size_t)row * d.nw + d.wlo + w] : 0ULL;
-      }
-    for (uint32_t t = tid; t < d.n_services; t += NT) L_nsv[t] = 0;
-  }
+  for (uint32_t w = tid; w < 2 * P * 64u; w += NT) L_drop[w] = 0;
+  if constexpr (!ZG)
+    for (uint32_t t = tid; t < dz * P * 64; t += NT) {
+      const uint32_t row = t / (P * 64), w = t % (P * 64);
+      L_zm[t] = w < nwords ? x.zmap[(size_t)row * d.nw + d.wlo + w] : 0ULL;
+    }
+  for (uint32_t t = tid; t < d.n_services; t += NT) L_nsv[t] = 0;
   __syncthreads();
   const uint64_t rng0 = *rng_io;
 
@@ -1423,9 +1406,8 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
     uint32_t wb_at[P], wm_at[P];
 #pragma unroll
     for (int q = 0; q < P; ++q) {
-      // lane l holds words l*P + q (ServiceAntiAffinity: the LDS-slot layout its
-      // re-rank walks), else q*64 + l (coalesced loads, bank-conflict-free LDS)
-      const uint32_t wq = ANTI ? lane * P + q : q * 64 + lane;
+      // lane l holds words l*P + q (the LDS-slot layout the re-rank walks)
+      const uint32_t wq = lane * P + q;
       uint32_t g = 0;
       for (uint32_t r = 1; r < x.world; ++r)
         if (wq >= x.wlo[r] && x.nw[r] > 0) g = r;
@@ -1487,22 +1469,8 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
         cnt += __popcll(t0[q]);
       }
       uint32_t incl = 0, k0 = 0;
-      // (q-major) per row q = words [64q, 64q + 64): the T0 bits below each lane's
-      // word in the row (ex_q) and below the row (rowex[q], wave-uniform)
-      uint32_t ex_q[P], rowex[P];
-      if constexpr (ANTI) {
-        incl = dpp_scan_add(cnt);
-        k0 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-      } else {
-#pragma unroll
-        for (int q = 0; q < P; ++q) {
-          const uint32_t c1 = (uint32_t)__popcll(t0[q]);
-          const uint32_t in1 = dpp_scan_add(c1);
-          ex_q[q] = in1 - c1;
-          rowex[q] = k0;
-          k0 += (uint32_t)__builtin_amdgcn_readlane((int)in1, 63);
-        }
-      }
+      incl = dpp_scan_add(cnt);
+      k0 = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
       pstamp(25);
       // draw index = drawable pods before j (every one of them known)
       uint32_t idx = 0;
@@ -1540,8 +1508,7 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
       int32_t s_cnt = 0, s_max = 0, s_peer = 0;
       if (drawable) {
         const uint32_t ix0 = __builtin_amdgcn_readfirstlane(mv);  // lane 0: r mod k0
-        if constexpr (ANTI) pred = (int32_t)select_in_lanes<P>(t0, cnt, incl, k0 - 1 - ix0, lane);
-        else pred = (int32_t)select_qmajor<P>(t0, ex_q, rowex, k0 - 1 - ix0, lane);
+        pred = (int32_t)select_in_lanes<P>(t0, cnt, incl, k0 - 1 - ix0, lane);
         const uint32_t pn = d.lo + (uint32_t)pred;
         if (lane == 0) pv = d.cap_cpu[pn];
         else if (lane == 1) pv = d.cap_mem[pn];
@@ -1556,60 +1523,38 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
       }
       r_mod[e * 64 + lane] = mv;
       if (lane < DW) r_rec[e * DW + lane] = rec;
-      if constexpr (ANTI) {
 #pragma unroll
-        for (int q = 0; q < P; ++q) r_t0[(size_t)e * P * 64 + lane * P + q] = t0[q];
-      } else {
-        // T0 by word, and the sparse select's prefix counts: T0 bits below each
-        // row (r_lp[q] = {below, up to the row's end}) and below each word within
-        // its row (r_wp, u16), so the ascending position of node n in T0 is
-        // r_lp[n >> 12] + r_wp[n >> 6] + the bits below n in its word
-        uint32_t lpe = 0, lpi = 0;
+      for (int q = 0; q < P; ++q) r_t0[(size_t)e * P * 64 + lane * P + q] = t0[q];
+      // fit at the snapshot, best-per-row nodes, row bests, domain counts
+      uint64_t bw[P];
 #pragma unroll
-        for (int q = 0; q < P; ++q) {
-          r_t0[(size_t)e * P * 64 + q * 64 + lane] = t0[q];
-          r_wp[(size_t)e * P * 64 + q * 64 + lane] = (uint16_t)ex_q[q];
-          if (lane == (uint32_t)q) {
-            lpe = rowex[q];
-            lpi = q + 1 < P ? rowex[q + 1 < P ? q + 1 : q] : k0;
-          }
-        }
-        if (lane < P) {
-          r_lp[(e * 64 + lane) * 2] = lpe;
-          r_lp[(e * 64 + lane) * 2 + 1] = lpi;
+      for (int q = 0; q < P; ++q) {
+        bw[q] = wb_at[q] != ~0u ? *reinterpret_cast<const uint64_t*>(x.buf + wb_at[q] + x.b_off + j * row_b) : 0ULL;
+        if constexpr (!FG) {
+          r_fit[(size_t)e * P * 64 + lane * P + q] =
+              wb_at[q] != ~0u ? *reinterpret_cast<const uint64_t*>(x.buf + wb_at[q] + x.fit_off + j * row_b) : 0ULL;
+          r_b[(size_t)e * P * 64 + lane * P + q] = bw[q];
         }
       }
-      if constexpr (ANTI) {  // fit at the snapshot, best-per-row nodes, row bests, domain counts
-        uint64_t bw[P];
+      // B nodes per domain row (the committer's re-rank subtracts the drops): counted here over
+      // the LDS row bitmaps, past 32k nodes by phase A (win2_zg)
+      int32_t kz = 0;
+      if constexpr (ZG) {
+        if (lane < dz) kz = x.dmb[(size_t)wcap * dz + (size_t)j * dz + lane];
+      } else {
+        for (uint32_t rw = 0; rw < dz; ++rw) {
+          uint32_t c1 = 0;
 #pragma unroll
-        for (int q = 0; q < P; ++q) {
-          bw[q] = wb_at[q] != ~0u ? *reinterpret_cast<const uint64_t*>(x.buf + wb_at[q] + x.b_off + j * row_b) : 0ULL;
-          if constexpr (!FG) {
-            r_fit[(size_t)e * P * 64 + lane * P + q] =
-                wb_at[q] != ~0u ? *reinterpret_cast<const uint64_t*>(x.buf + wb_at[q] + x.fit_off + j * row_b) : 0ULL;
-            r_b[(size_t)e * P * 64 + lane * P + q] = bw[q];
-          }
+          for (int q = 0; q < P; ++q) c1 += __popcll(bw[q] & L_zm[(size_t)rw * P * 64 + lane * P + q]);
+          const uint32_t tr = wave_total_add(c1);
+          if (lane == rw) kz = (int32_t)tr;
         }
-        // B nodes per domain row (the committer's re-rank subtracts the drops): counted here over
-        // the LDS row bitmaps, past 32k nodes by phase A (win2_zg)
-        int32_t kz = 0;
-        if constexpr (ZG) {
-          if (lane < dz) kz = x.dmb[(size_t)wcap * dz + (size_t)j * dz + lane];
-        } else {
-          for (uint32_t rw = 0; rw < dz; ++rw) {
-            uint32_t c1 = 0;
-#pragma unroll
-            for (int q = 0; q < P; ++q) c1 += __popcll(bw[q] & L_zm[(size_t)rw * P * 64 + lane * P + q]);
-            const uint32_t tr = wave_total_add(c1);
-            if (lane == rw) kz = (int32_t)tr;
-          }
-        }
-        if (lane < dz) r_kz[e * KSG_RR_MAXZ + lane] = kz;
-        if (lane < dz) {
-          r_mb[e * KSG_RR_MAXZ + lane] = x.dmb[(size_t)j * dz + lane];
-          r_dc[e * KSG_RR_MAXZ + lane] =
-              lane + 1 < dz ? x.dcnt[(size_t)j * d.n_domains_total + d.anti_dom_off[0] + lane] : 0;
-        }
+      }
+      if (lane < dz) r_kz[e * KSG_RR_MAXZ + lane] = kz;
+      if (lane < dz) {
+        r_mb[e * KSG_RR_MAXZ + lane] = x.dmb[(size_t)j * dz + lane];
+        r_dc[e * KSG_RR_MAXZ + lane] =
+            lane + 1 < dz ? x.dcnt[(size_t)j * d.n_domains_total + d.anti_dom_off[0] + lane] : 0;
       }
       if (inl && lane < n_svcs) {
         r_svc[e].cnt[lane] = s_cnt;
@@ -1690,10 +1635,8 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
         S.node = woff;
         S.dl_c = S.dl_m = 0;
         S.smask = 0;
-        if constexpr (ANTI) {
-          const int32_t dm = gld(d.anti_domain + wn);  // (first anti priority: the re-rank's domain rows)
-          S.row = dm >= 0 ? (uint32_t)dm : ~0u;
-        }
+        const int32_t dm = gld(d.anti_domain + wn);  // (first anti priority: the re-rank's domain rows)
+        S.row = dm >= 0 ? (uint32_t)dm : ~0u;
       }
       uint32_t new_mask = 0;
       if (n_svcs) {
@@ -1758,127 +1701,80 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
       cstamp(c == 0 ? 17 : 20);
       const uint32_t rec = lane < DW ? r_rec[e * DW + lane] : 0u;
       const int32_t m0 = (int32_t)__builtin_amdgcn_readfirstlane(r_hdr[e].m0);
+      // the pod against this lane's slot as of commits <= i-2: a drop among the
+      // nodes at their domain row's best (B; T0 drops counted for the fast
+      // path), the domain-count stop, and the window's commits of the pod's
+      // service the slot adds to its row's count while the pod still fits it
       uint32_t cntd = 0;
-      uint64_t dmsk = 0;
-      if constexpr (ANTI) {
-        // the pod against this lane's slot as of commits <= i-2: a drop among the
-        // nodes at their domain row's best (B; T0 drops counted for the fast
-        // path), the domain-count stop, and the window's commits of the pod's
-        // service the slot adds to its row's count while the pod still fits it
-        bool drop = false, t0d = false, astop = false;
-        uint32_t ks = 0;
-        cstamp(c == 0 ? 22 : 40);  // (checker 0: the pod's record; lane 40 is dropped)
-        if (!__builtin_amdgcn_readlane(rec, WS_ERR) && m0 != KSG_S32_NONE && S.node != ~0u) {
-          const PodView pv = pod_view(rec);
-          const uint32_t wd = S.node >> 6;
-          const uint64_t nb = 1ULL << (S.node & 63);
-          SlotRow R;  // the slot's lists, in registers (in flight with the slot's T0 / B / fit words)
-          R.load(my_cl);
-          const bool in_t0 = (r_t0[(size_t)e * P * 64 + wd] & nb) != 0;
-          const bool in_b = ((FG ? pa_word(x.b_off, i, wd) : r_b[(size_t)e * P * 64 + wd]) & nb) != 0;
-          const bool fsnap = pv.s >= 0 && ((FG ? pa_word(x.fit_off, i, wd) : r_fit[(size_t)e * P * 64 + wd]) & nb) != 0;
-          if (in_b || fsnap) {
-            const int64_t now_c = (int64_t)((uint64_t)S.snp_c + (uint64_t)S.dl_c);
-            const int64_t now_m = (int64_t)((uint64_t)S.snp_m + (uint64_t)S.dl_m);
-            bool nofit = false;
-            if (res_on && !pv.zero_req)  // PodFitsResources (predicates.go:127-145)
-              nofit = !((S.cap_c == 0 || S.cap_c - now_c >= pv.req_c) && (S.cap_m == 0 || S.cap_m - now_m >= pv.req_m));
-            if (!nofit && pv.nk && S.nk)  // PodFitsPorts / NoDiskConflict vs the window's keys
-              nofit |= R.key_hit(S.nk, rec, pv.nk, pv.n_ports, ports_on, disk_on);
-            if (in_b) {
-              drop = nofit;
-              if (!drop && d.w_lr) {  // LeastRequested (priorities.go:43-76)
-                // (branch-free terms: the four interleave)
-                const int32_t lr_now =
-                    lr_win_nb(now_c + pv.req_c, S.cap_c, S.inv_c) + lr_win_nb(now_m + pv.req_m, S.cap_m, S.inv_m);
-                const int32_t lr_snap =
-                    lr_win_nb(S.snp_c + pv.req_c, S.cap_c, S.inv_c) + lr_win_nb(S.snp_m + pv.req_m, S.cap_m, S.inv_m);
-                drop = (lr_now >> 1) != (lr_snap >> 1);
-              }
-              if (!drop && spread_on && pv.s >= 0 && ((S.smask >> (pv.s & 31)) & 1u)) {
-                int32_t delta = 0, snapc = 0;  // ServiceSpreading (spreading.go:72-86) under an unchanged maxCount
-                R.svc(S.ns, (uint32_t)pv.s, snapc, delta);
-                if (delta)
-                  drop = frac10_i32(pv.smax - snapc - delta, pv.smax) !=
-                         frac10_i32(pv.smax - snapc, pv.smax);
-              }
-              if (drop)
-                atomicOr(reinterpret_cast<unsigned long long*>(L_drop + (size_t)par * P * 64 + wd), nb);
-              t0d = drop && in_t0;
-            }
-            if (fsnap) {
-              if (nofit) {
-                astop = anti_counts_move(d, S.node, pv.s);
-              } else if ((S.smask >> (pv.s & 31)) & 1u) {
-                int32_t sc_ = 0, kn_ = 0;
-                R.svc(S.ns, (uint32_t)pv.s, sc_, kn_);
-                ks = (uint32_t)kn_;
-              }
-            }
-          }
-        }
-        cstamp(c == 0 ? 23 : 40);  // (checker 0: the slot's check)
-        cntd = __popcll(__ballot(t0d));
-        // per domain row: the B drops (unlabelled nodes: row dz-1) and the window commits of the
-        // pod's service on slots it still fits, summed by LDS atomics after the rows are zeroed
-        // (one wave's LDS operations run in issue order)
-        int32_t* const ddr = L_ddr + (c * 2 + par) * KSG_RR_MAXZ;
-        int32_t* const dca = L_dca + (c * 2 + par) * KSG_RR_MAXZ;
-        if (lane < dz) {
-          ddr[lane] = 0;
-          dca[lane] = 0;
-        }
-        if (drop) atomicAdd(&ddr[S.row != ~0u ? S.row : dz - 1], 1);
-        if (ks != 0 && S.row != ~0u) atomicAdd(&dca[S.row], (int32_t)ks);
-        const uint32_t ast = __ballot(astop) != 0;
-        if (lane == 0) ctl->chk_stop[c][par] = ast;
-      } else if (!__builtin_amdgcn_readlane(rec, WS_ERR) && m0 != KSG_S32_NONE) {
+      bool drop = false, t0d = false, astop = false;
+      uint32_t ks = 0;
+      cstamp(c == 0 ? 22 : 40);  // (checker 0: the pod's record; lane 40 is dropped)
+      if (!__builtin_amdgcn_readlane(rec, WS_ERR) && m0 != KSG_S32_NONE && S.node != ~0u) {
         const PodView pv = pod_view(rec);
-        bool drop = false;
-        uint32_t dpos = 0;
-        if (S.node != ~0u) {
-          const uint64_t* t0e = r_t0 + (size_t)e * P * 64;
-          const uint32_t wd = S.node >> 6;
-          const uint64_t tw = t0e[wd];
-          SlotRow R;  // the slot's lists, in registers (in flight with the T0 word)
-          R.load(my_cl);
-          // the node's ascending position in T0 (used only if it drops)
-          dpos = r_lp[(e * 64 + (wd >> 6)) * 2] + r_wp[(size_t)e * P * 64 + wd] +
-                 (uint32_t)__popcll(tw & ((1ULL << (S.node & 63)) - 1ULL));
-          if ((tw >> (S.node & 63)) & 1ULL) {
-            // does the slot (a snapshot tie of the pod) score below M0 now?
-            const int64_t now_c = (int64_t)((uint64_t)S.snp_c + (uint64_t)S.dl_c);
-            const int64_t now_m = (int64_t)((uint64_t)S.snp_m + (uint64_t)S.dl_m);
-            if (res_on && !pv.zero_req)  // PodFitsResources (predicates.go:127-145)
-              drop = !((S.cap_c == 0 || S.cap_c - now_c >= pv.req_c) && (S.cap_m == 0 || S.cap_m - now_m >= pv.req_m));
-            if (d.w_lr) {  // LeastRequested (priorities.go:43-76) can only fall as requested grows
-              const int32_t lr_now = lr_win(now_c + pv.req_c, S.cap_c, S.inv_c) + lr_win(now_m + pv.req_m, S.cap_m, S.inv_m);
+        const uint32_t wd = S.node >> 6;
+        const uint64_t nb = 1ULL << (S.node & 63);
+        SlotRow R;  // the slot's lists, in registers (in flight with the slot's T0 / B / fit words)
+        R.load(my_cl);
+        const bool in_t0 = (r_t0[(size_t)e * P * 64 + wd] & nb) != 0;
+        const bool in_b = ((FG ? pa_word(x.b_off, i, wd) : r_b[(size_t)e * P * 64 + wd]) & nb) != 0;
+        const bool fsnap = pv.s >= 0 && ((FG ? pa_word(x.fit_off, i, wd) : r_fit[(size_t)e * P * 64 + wd]) & nb) != 0;
+        if (in_b || fsnap) {
+          const int64_t now_c = (int64_t)((uint64_t)S.snp_c + (uint64_t)S.dl_c);
+          const int64_t now_m = (int64_t)((uint64_t)S.snp_m + (uint64_t)S.dl_m);
+          bool nofit = false;
+          if (res_on && !pv.zero_req)  // PodFitsResources (predicates.go:127-145)
+            nofit = !((S.cap_c == 0 || S.cap_c - now_c >= pv.req_c) && (S.cap_m == 0 || S.cap_m - now_m >= pv.req_m));
+          if (!nofit && pv.nk && S.nk)  // PodFitsPorts / NoDiskConflict vs the window's keys
+            nofit |= R.key_hit(S.nk, rec, pv.nk, pv.n_ports, ports_on, disk_on);
+          if (in_b) {
+            drop = nofit;
+            if (!drop && d.w_lr) {  // LeastRequested (priorities.go:43-76)
+              // (branch-free terms: the four interleave)
+              const int32_t lr_now =
+                  lr_win_nb(now_c + pv.req_c, S.cap_c, S.inv_c) + lr_win_nb(now_m + pv.req_m, S.cap_m, S.inv_m);
               const int32_t lr_snap =
-                  lr_win(S.snp_c + pv.req_c, S.cap_c, S.inv_c) + lr_win(S.snp_m + pv.req_m, S.cap_m, S.inv_m);
-              drop |= (lr_now >> 1) != (lr_snap >> 1);
+                  lr_win_nb(S.snp_c + pv.req_c, S.cap_c, S.inv_c) + lr_win_nb(S.snp_m + pv.req_m, S.cap_m, S.inv_m);
+              drop = (lr_now >> 1) != (lr_snap >> 1);
             }
-            if (!drop && pv.nk && S.nk)  // PodFitsPorts / NoDiskConflict vs the window's keys
-              drop |= R.key_hit(S.nk, rec, pv.nk, pv.n_ports, ports_on, disk_on);
             if (!drop && spread_on && pv.s >= 0 && ((S.smask >> (pv.s & 31)) & 1u)) {
-              // ServiceSpreading (spreading.go:72-86) under an unchanged maxCount
-              int32_t delta = 0, snapc = 0;
+              int32_t delta = 0, snapc = 0;  // ServiceSpreading (spreading.go:72-86) under an unchanged maxCount
               R.svc(S.ns, (uint32_t)pv.s, snapc, delta);
               if (delta)
                 drop = frac10_i32(pv.smax - snapc - delta, pv.smax) !=
                        frac10_i32(pv.smax - snapc, pv.smax);
             }
+            if (drop)
+              atomicOr(reinterpret_cast<unsigned long long*>(L_drop + (size_t)par * P * 64 + wd), nb);
+            t0d = drop && in_t0;
+          }
+          if (fsnap) {
+            if (nofit) {
+              astop = anti_counts_move(d, S.node, pv.s);
+            } else if ((S.smask >> (pv.s & 31)) & 1u) {
+              int32_t sc_ = 0, kn_ = 0;
+              R.svc(S.ns, (uint32_t)pv.s, sc_, kn_);
+              ks = (uint32_t)kn_;
+            }
           }
         }
-        if (drop) L_dpos[par * KSG_MAX_SLOTS + my_slot] = dpos;
-        dmsk = __ballot(drop);
-        cntd = __popcll(dmsk);
       }
+      cstamp(c == 0 ? 23 : 40);  // (checker 0: the slot's check)
+      cntd = __popcll(__ballot(t0d));
+      // per domain row: the B drops (unlabelled nodes: row dz-1) and the window commits of the
+      // pod's service on slots it still fits, summed by LDS atomics after the rows are zeroed
+      // (one wave's LDS operations run in issue order)
+      int32_t* const ddr = L_ddr + (c * 2 + par) * KSG_RR_MAXZ;
+      int32_t* const dca = L_dca + (c * 2 + par) * KSG_RR_MAXZ;
+      if (lane < dz) {
+        ddr[lane] = 0;
+        dca[lane] = 0;
+      }
+      if (drop) atomicAdd(&ddr[S.row != ~0u ? S.row : dz - 1], 1);
+      if (ks != 0 && S.row != ~0u) atomicAdd(&dca[S.row], (int32_t)ks);
+      const uint32_t ast = __ballot(astop) != 0;
+      if (lane == 0) ctl->chk_stop[c][par] = ast;
       if (lane == 0) {
         ctl->chk_cnt[c][par] = cntd;
-        if constexpr (!ANTI) {
-          ctl->chk_msk[c][par][0] = (uint32_t)dmsk;
-          ctl->chk_msk[c][par][1] = (uint32_t)(dmsk >> 32);
-        }
         st_post(&ctl->chk_seq[c], i + 1);
       }
       cstamp(c == 0 ? 18 : 21);
@@ -1990,9 +1886,7 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
       const bool sv_lane = lane < n_svcs;
       const uint32_t my_sv =
           (uint32_t)__shfl((int)prec, (int)min(WS_IDS + pnk + n_sel + (sv_lane ? lane : 0u), 63u), 64);
-      if constexpr (ANTI) {  // (re-rank) the service's window commits: its pod count n moved
-        if (sv_lane) atomicAdd(&L_nsv[my_sv], 1u);
-      }
+      if (sv_lane) atomicAdd(&L_nsv[my_sv], 1u);  // (re-rank) the service's window commits: its pod count n moved
       int32_t mx = 0, peer = 0, cnt = 0;
       if (sv_lane) {
         cnt = gld(d.svc_cnt + (size_t)my_sv * d.n_nodes + wn);
@@ -2092,7 +1986,7 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
         usev = gld(use_src + xw);
         invv = gld(inv_src + xw);
         xcv = gld(d.svc_cnt + (size_t)(s >= 0 ? s : 0) * d.n_nodes + xw);
-        if constexpr (ANTI) xdm = gld(d.anti_domain + xw);
+        xdm = gld(d.anti_domain + xw);
       }
       uint32_t xst = 0, xrow = ~0u;  // (re-rank) domain-count stop; row of x and its count correction
       int32_t xcorr = 0;
@@ -2155,50 +2049,46 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
           }
           xd |= __ballot(hit) != 0;
         }
-        if constexpr (ANTI) {
-          xrw = xdm >= 0 ? (uint32_t)xdm : dz - 1;
-          // x as of commit i-1 and as of i-2 (the checkers' view of it): does the
-          // pod still fit it (PodFitsResources, host ports, PDs), and its
-          // service's window commits there; the domain count of x's row moves by
-          // the difference, or the window ends if the pod no longer fits a
-          // labelled x that held pods of its service at the snapshot
-          const uint64_t xfw = FG ? pa_word(x.fit_off, i, xnode >> 6) : r_fit[(size_t)e * P * 64 + (xnode >> 6)];
-          if (s >= 0 && ((xfw >> (xnode & 63)) & 1ULL)) {
-            const PodView qv = pod_view(prec);
-            const int64_t befv = (int64_t)((uint64_t)nowv - (uint64_t)(rl ? qv.req_m : qv.req_c));
-            bool fa = true, fb = true;
-            if (res_on && !pv.zero_req) {
-              fa = (__ballot(lane < 2 && !(capv == 0 || capv - nowv >= reqv)) & 3ULL) == 0;
-              fb = (__ballot(lane < 2 && !(capv == 0 || capv - befv >= reqv)) & 3ULL) == 0;
+        xrw = xdm >= 0 ? (uint32_t)xdm : dz - 1;
+        // x as of commit i-1 and as of i-2 (the checkers' view of it): does the
+        // pod still fit it (PodFitsResources, host ports, PDs), and its
+        // service's window commits there; the domain count of x's row moves by
+        // the difference, or the window ends if the pod no longer fits a
+        // labelled x that held pods of its service at the snapshot
+        const uint64_t xfw = FG ? pa_word(x.fit_off, i, xnode >> 6) : r_fit[(size_t)e * P * 64 + (xnode >> 6)];
+        if (s >= 0 && ((xfw >> (xnode & 63)) & 1ULL)) {
+          const PodView qv = pod_view(prec);
+          const int64_t befv = (int64_t)((uint64_t)nowv - (uint64_t)(rl ? qv.req_m : qv.req_c));
+          bool fa = true, fb = true;
+          if (res_on && !pv.zero_req) {
+            fa = (__ballot(lane < 2 && !(capv == 0 || capv - nowv >= reqv)) & 3ULL) == 0;
+            fb = (__ballot(lane < 2 && !(capv == 0 || capv - befv >= reqv)) & 3ULL) == 0;
+          }
+          if (nk && xnk) {
+            bool ha = false, hb = false;
+            for (uint32_t b = 0; b < nk; ++b) {
+              const bool on = b < pv.n_ports ? ports_on : disk_on;
+              const bool eq = on && xcl == (uint32_t)__builtin_amdgcn_readlane((int)rec, (int)(WS_IDS + b));
+              ha |= eq && kt < xnk;
+              hb |= eq && kt < bnk;
             }
-            if (nk && xnk) {
-              bool ha = false, hb = false;
-              for (uint32_t b = 0; b < nk; ++b) {
-                const bool on = b < pv.n_ports ? ports_on : disk_on;
-                const bool eq = on && xcl == (uint32_t)__builtin_amdgcn_readlane((int)rec, (int)(WS_IDS + b));
-                ha |= eq && kt < xnk;
-                hb |= eq && kt < bnk;
-              }
-              fa = fa && __ballot(ha) == 0;
-              fb = fb && __ballot(hb) == 0;
-            }
-            const uint32_t kb = (uint32_t)__popcll(__ballot(s_ent && ut < bns));
-            if (!fa && xdm >= 0 && xcv > 0) xst = 1;
-            if (xdm >= 0) {
-              xrow = (uint32_t)xdm;
-              xcorr = (fa ? (int32_t)x_cnt_s : 0) - ((x_in_c && fb) ? (int32_t)kb : 0);
-            }
+            fa = fa && __ballot(ha) == 0;
+            fb = fb && __ballot(hb) == 0;
+          }
+          const uint32_t kb = (uint32_t)__popcll(__ballot(s_ent && ut < bns));
+          if (!fa && xdm >= 0 && xcv > 0) xst = 1;
+          if (xdm >= 0) {
+            xrow = (uint32_t)xdm;
+            xcorr = (fa ? (int32_t)x_cnt_s : 0) - ((x_in_c && fb) ? (int32_t)kb : 0);
           }
         }
         res = (xd ? 1u : 0u) | (flag_x ? 2u : 0u) | (xst ? 4u : 0u);
       }
       if (lane == 0) {
-        if constexpr (ANTI) {
-          ctl->xdz[par] = xrow;
-          ctl->xdc[par] = xcorr;
-          ctl->xrw[par] = xrw;
-          ctl->xnsv[par] = s >= 0 ? L_nsv[s] : 0u;
-        }
+        ctl->xdz[par] = xrow;
+        ctl->xdc[par] = xcorr;
+        ctl->xrw[par] = xrw;
+        ctl->xnsv[par] = s >= 0 ? L_nsv[s] : 0u;
         ctl->xres[par] = res;
         if constexpr (STAMP) ctl->t_x = (uint32_t)__builtin_amdgcn_s_memtime();
         st_post(&ctl->xseq, i + 1);
@@ -2249,7 +2139,6 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
   uint32_t ss0 = 0, ss1 = 0;      // their service entry counts
   int64_t dc0 = 0, dm0 = 0, dc1 = 0, dm1 = 0;  // their window deltas (current through the last commit)
   uint32_t xnode = 0;                    // node of the last commit (pod i-1)
-  uint32_t xslot = 0;                    // and its slot
   bool have_x = false;
   uint32_t prev_sv = ~0u;                // (ServiceAntiAffinity) services of commit i-1, lane t < count
   uint64_t t_last = 0, t_acc = 0;
@@ -2295,25 +2184,12 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
     const uint32_t rmod = r_mod[e * 64 + lane];
     const uint64_t* t0e = r_t0 + (size_t)e * P * 64;
     uint64_t t0w[P];
-    uint32_t lp_ex = 0, lp_in = 0, xlp = 0, xwp = 0;
-    uint64_t t0x = 0;
-    if constexpr (ANTI) {
+    // (unused, as msk0 .. dp1 below: without them the compiler promotes the committer's locals in
+    // another order and allocates other registers; they go with a change that is measured)
+    [[maybe_unused]] uint32_t lp_ex = 0, lp_in = 0, xlp = 0, xwp = 0;
+    [[maybe_unused]] uint64_t t0x = 0;
 #pragma unroll
-      for (int q = 0; q < P; ++q) t0w[q] = t0e[lane * P + q];
-    } else {
-      // the sparse select's row prefixes (lane q < P: row q), and where commit
-      // i-1's node sits in T0
-      if (lane < P) {
-        lp_ex = r_lp[(e * 64 + lane) * 2];
-        lp_in = r_lp[(e * 64 + lane) * 2 + 1];
-      }
-      if (have_x) {
-        const uint32_t xw = xnode >> 6;
-        t0x = t0e[xw];
-        xwp = r_wp[(size_t)e * P * 64 + xw];
-        xlp = r_lp[(e * 64 + (xw >> 6)) * 2];
-      }
-    }
+    for (int q = 0; q < P; ++q) t0w[q] = t0e[lane * P + q];
     const int32_t m0 = (int32_t)__builtin_amdgcn_readfirstlane(r_hdr[e].m0);
     const uint32_t k0 = __builtin_amdgcn_readfirstlane(r_hdr[e].k0);
     const int32_t pred = (int32_t)__builtin_amdgcn_readfirstlane(r_hdr[e].pred);
@@ -2369,44 +2245,28 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
     const uint32_t xr = ctl->xres[par];
     const uint32_t fw = s >= 0 ? L_flag[s >> 5] : 0u;
     uint64_t dww[P];
-    uint64_t msk0 = 0, msk1 = 0;
-    uint32_t dp0 = 0, dp1 = 0;
-    if constexpr (ANTI) {
+    [[maybe_unused]] uint64_t msk0 = 0, msk1 = 0;
+    [[maybe_unused]] uint32_t dp0 = 0, dp1 = 0;
 #pragma unroll
-      for (int q = 0; q < P; ++q) dww[q] = dw[lane * P + q];
-    } else {  // the checkers' dropping slots and the drops' positions in T0
-      msk0 = ((uint64_t)__builtin_amdgcn_readfirstlane(ctl->chk_msk[0][par][1]) << 32) |
-             (uint32_t)__builtin_amdgcn_readfirstlane(ctl->chk_msk[0][par][0]);
-      msk1 = ((uint64_t)__builtin_amdgcn_readfirstlane(ctl->chk_msk[1][par][1]) << 32) |
-             (uint32_t)__builtin_amdgcn_readfirstlane(ctl->chk_msk[1][par][0]);
-      dp0 = L_dpos[par * KSG_MAX_SLOTS + lane];
-      dp1 = L_dpos[par * KSG_MAX_SLOTS + 64 + lane];
-    }
+    for (int q = 0; q < P; ++q) dww[q] = dw[lane * P + q];
     const uint32_t xres = __builtin_amdgcn_readfirstlane(xr);
     if (s >= 0 && (spread_on || aff_on) && ((xres & 2u) || ((__builtin_amdgcn_readfirstlane(fw) >> (s & 31)) & 1u))) {
       resolved = i;  // a service scalar this pod reads changed in the window
       reason = KSG_STOP_SERVICE;
       break;
     }
-    uint32_t mv_n = 0;  // (ServiceAntiAffinity) window commits of the pod's service before it
-    if constexpr (ANTI) {
-      if ((xres & 4u) || __builtin_amdgcn_readfirstlane(ctl->chk_stop[0][par] | ctl->chk_stop[1][par])) {
-        resolved = i;  // the pod's domain counts moved: a fitted node holding its service's pods left its filter
-        reason = KSG_STOP_SERVICE;
-        break;
-      }
-      if (s >= 0)
-        mv_n = __builtin_amdgcn_readfirstlane(ctl->xnsv[par]) + (__ballot(prev_sv == (uint32_t)s) != 0 ? 1u : 0u);
+    if ((xres & 4u) || __builtin_amdgcn_readfirstlane(ctl->chk_stop[0][par] | ctl->chk_stop[1][par])) {
+      resolved = i;  // the pod's domain counts moved: a fitted node holding its service's pods left its filter
+      reason = KSG_STOP_SERVICE;
+      break;
     }
+    uint32_t mv_n = 0;  // window commits of the pod's service before it
+    if (s >= 0)
+      mv_n = __builtin_amdgcn_readfirstlane(ctl->xnsv[par]) + (__ballot(prev_sv == (uint32_t)s) != 0 ? 1u : 0u);
     const bool moved = mv_n != 0;
     uint32_t dropped = __builtin_amdgcn_readfirstlane(cc0) + __builtin_amdgcn_readfirstlane(cc1);
     bool x_drop = false;
-    if constexpr (!ANTI) {
-      // x counts as a new drop iff it is a snapshot tie whose slot the checkers
-      // kept (a new slot: they have not seen it)
-      const bool x_kept = !(((xslot < 64 ? msk0 : msk1) >> (xslot & 63)) & 1ULL);
-      x_drop = have_x && (xres & 1u) && ((t0x >> (xnode & 63)) & 1ULL) && x_kept;
-    } else if (have_x && (xres & 1u)) {  // x counts as a new drop iff it was a snapshot tie the checkers kept
+    if (have_x && (xres & 1u)) {  // x counts as a new drop iff it was a snapshot tie the checkers kept
       const uint32_t xwd = xnode >> 6, xo = xwd / P, xq = xwd % P;
       uint64_t t0x = 0, dwx = 0;
 #pragma unroll
@@ -2516,43 +2376,6 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
       KSG_COUNT2(12, __builtin_amdgcn_s_memtime() - t_rr)  // (the re-rank's cycles)
     } else if (dropped == 0) {
       woff = (uint32_t)pred;  // staged by the producer
-    } else if constexpr (!ANTI) {
-      // ---- sparse select: the live ties are T0 minus the drops, whose
-      // ascending T0 positions are known (the checkers' and x's). The (k-1-ix)-th
-      // live tie ascending is T0's tp-th, tp the least fixed point of
-      // tp = t + #(drops at positions <= tp); then its lane (lane prefixes), its
-      // word (the owner lane's word prefixes) and its bit (mbcnt rank)
-      KSG_COUNT2(7, 64)
-      uint32_t ix;
-      if (dropped < 64) {
-        ix = (uint32_t)__builtin_amdgcn_readlane((int)rmod, (int)dropped);
-      } else {
-        const uint64_t r = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(r_hdr[e].r >> 32)) << 32) |
-                           (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)r_hdr[e].r);
-        ix = umod64_32(r, k);
-      }
-      const uint32_t t = k - 1 - ix;
-      const uint32_t d0 = ((msk0 >> lane) & 1ULL) ? dp0 : ~0u;
-      const uint32_t d1 = ((msk1 >> lane) & 1ULL) ? dp1 : ~0u;
-      const uint32_t xpos = x_drop ? xlp + xwp + (uint32_t)__popcll(t0x & ((1ULL << (xnode & 63)) - 1ULL)) : ~0u;
-      uint32_t tp = t;
-      for (;;) {
-        const uint32_t cnt = (uint32_t)__popcll(__ballot(d0 <= tp)) + (uint32_t)__popcll(__ballot(d1 <= tp)) +
-                             (xpos <= tp ? 1u : 0u);
-        if (t + cnt == tp) break;
-        tp = t + cnt;
-      }
-      const uint32_t qs = (uint32_t)__builtin_ctzll(__ballot(lane < P && lp_ex <= tp && tp < lp_in));
-      const uint32_t loc = tp - (uint32_t)__builtin_amdgcn_readlane((int)lp_ex, (int)qs);
-      const uint64_t w = t0e[qs * 64 + lane];
-      const uint32_t wpq = r_wp[(size_t)e * P * 64 + qs * 64 + lane];
-      const uint32_t ls = (uint32_t)__builtin_ctzll(__ballot(wpq <= loc && loc < wpq + (uint32_t)__popcll(w)));
-      const uint64_t ws = readlane64(w, (int)ls);
-      const uint32_t lw = loc - (uint32_t)__builtin_amdgcn_readlane((int)wpq, (int)ls);
-      const uint32_t rank =
-          __builtin_amdgcn_mbcnt_hi((uint32_t)(ws >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ws, 0u));
-      const uint32_t bsel = (uint32_t)__builtin_ctzll(__ballot(((ws >> lane) & 1ULL) && rank == lw));
-      woff = (qs * 64 + ls) * 64 + bsel;
     } else {
       KSG_COUNT2(7, 64)
       uint32_t ix;
@@ -2576,11 +2399,10 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
       const uint32_t incl = dpp_scan_add(cl);
       woff = select_in_lanes<P>(live, cl, incl, k - 1 - ix, lane);
     }
-    if constexpr (ANTI) {  // (drops outside T0 are scattered too) clear them for the pod two ahead
+    // (drops outside T0 are scattered too) clear them for the pod two ahead
 #pragma unroll
-      for (int q = 0; q < P; ++q)
-        if (dww[q]) dw[lane * P + q] = 0;
-    }
+    for (int q = 0; q < P; ++q)
+      if (dww[q]) dw[lane * P + q] = 0;
     if (lane == 0) {  // the x-checker loads the node's snapshot meanwhile
       L_cm[i].xn = woff;
       if constexpr (STAMP) ctl->t_n = (uint32_t)__builtin_amdgcn_s_memtime();
@@ -2649,11 +2471,8 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
     }
     have_x = true;
     xnode = woff;
-    xslot = slot;
-    if constexpr (ANTI) {
-      const uint32_t sv_t = (uint32_t)__shfl((int)rec, (int)min(WS_IDS + nk + n_sel + (lane < n_svcs ? lane : 0u), 63u), 64);
-      prev_sv = lane < n_svcs ? sv_t : ~0u;
-    }
+    const uint32_t sv_t = (uint32_t)__shfl((int)rec, (int)min(WS_IDS + nk + n_sel + (lane < n_svcs ? lane : 0u), 63u), 64);
+    prev_sv = lane < n_svcs ? sv_t : ~0u;
     ++n_draws;
     KSG_STAMP2(5)
   }
@@ -2674,11 +2493,10 @@ __global__ __launch_bounds__(512) void ksg_win_resolve2_kernel(KsgDev d, uint32_
     }
   }
   if (!drained || ld_acq(&ctl->hang)) reason = KSG_STOP_HANG;
-  if constexpr (ANTI) {  // the producers staged this window's domain counts and row bests: reset them for the next
-    for (uint32_t t = lane; t < x.dcnt_n; t += 64) x.dcnt[t] = 0;
-    for (uint32_t t = lane; t < wcap * dz; t += 64) x.dmb[t] = KSG_S32_NONE;
-    for (uint32_t t = lane; t < wcap * dz; t += 64) x.dmb[(size_t)wcap * dz + t] = 0;  // (B counts per row)
-  }
+  // the producers staged this window's domain counts and row bests: reset them for the next
+  for (uint32_t t = lane; t < x.dcnt_n; t += 64) x.dcnt[t] = 0;
+  for (uint32_t t = lane; t < wcap * dz; t += 64) x.dmb[t] = KSG_S32_NONE;
+  for (uint32_t t = lane; t < wcap * dz; t += 64) x.dmb[(size_t)wcap * dz + t] = 0;  // (B counts per row)
   if constexpr (STAMP) {
     if (d.dbgbuf && lane < 16) atomicAdd(d.dbgbuf + lane, (int32_t)(t_acc / 64));
   }
@@ -2733,37 +2551,29 @@ hipError_t ksg_launch_win_eval(const KsgDev& d, int mode, const ksg_pod* batch, 
   const uint32_t pg = small ? KSG_PG_SMALL : KSG_PG_LARGE;
   // one dimension, a multiple of 8 workgroups (the kernel's XCD-aware order)
   const dim3 grid((gx * ((wcap + pg - 1) / pg) + 7) & ~7u);
-#define KSG_EVAL_LAUNCH(M, G)                                                                                    \
-  hipLaunchKernelGGL((ksg_win_score_kernel<M, G>), grid, dim3(KSG_SC_NT), 0, st, d, batch, ids, run, wcap, sums, \
-                     wbits, wmax, ostride, dcnt, wfit, dmb, wbz, dz, nullptr, nullptr, nullptr, nullptr)
-#define KSG_EVAL_LAUNCH_X(M, G)                                                                              \
-  hipLaunchKernelGGL((ksg_win_score_kernel<M, G, true>), grid, dim3(KSG_SC_NT), 0, st, d, batch, ids, \
-                     run, wcap, sums, wbits, wmax, ostride, dcnt, wfit, dmb, wbz, dz, exts, tmax, psoft, thist)
-  if (exts && mode == KSG_WIN_TMAX) {  // extensions: the TaintToleration count pass
-    if (small) KSG_EVAL_LAUNCH_X(KSG_WIN_TMAX, KSG_PG_SMALL);
-    else KSG_EVAL_LAUNCH_X(KSG_WIN_TMAX, KSG_PG_LARGE);
-  } else if (exts && mode == KSG_WIN_COUNT) {  // ServiceAntiAffinity with the extension filters (round 6:
-    // taints only, no extension scores, no extended-resource requests in the batch; use_window)
-    if (small) KSG_EVAL_LAUNCH_X(KSG_WIN_COUNT, KSG_PG_SMALL);
-    else KSG_EVAL_LAUNCH_X(KSG_WIN_COUNT, KSG_PG_LARGE);
-  } else if (exts && mode == KSG_WIN_ANTI) {
-    if (small) KSG_EVAL_LAUNCH_X(KSG_WIN_ANTI, KSG_PG_SMALL);
-    else KSG_EVAL_LAUNCH_X(KSG_WIN_ANTI, KSG_PG_LARGE);
-  } else if (exts) {  // extensions, plain mode
-    if (small) KSG_EVAL_LAUNCH_X(KSG_WIN_PLAIN, KSG_PG_SMALL);
-    else KSG_EVAL_LAUNCH_X(KSG_WIN_PLAIN, KSG_PG_LARGE);
-  } else if (mode == KSG_WIN_COUNT) {
-    if (small) KSG_EVAL_LAUNCH(KSG_WIN_COUNT, KSG_PG_SMALL);
-    else KSG_EVAL_LAUNCH(KSG_WIN_COUNT, KSG_PG_LARGE);
-  } else if (mode == KSG_WIN_ANTI) {
-    if (small) KSG_EVAL_LAUNCH(KSG_WIN_ANTI, KSG_PG_SMALL);
-    else KSG_EVAL_LAUNCH(KSG_WIN_ANTI, KSG_PG_LARGE);
-  } else {
-    if (small) KSG_EVAL_LAUNCH(KSG_WIN_PLAIN, KSG_PG_SMALL);
-    else KSG_EVAL_LAUNCH(KSG_WIN_PLAIN, KSG_PG_LARGE);
+  const bool ext = exts != nullptr;
+  if (!ext) tmax = nullptr, psoft = nullptr, thist = nullptr;  // (the kernel takes them with the extensions only)
+  // KSG_WIN_TMAX is the extensions' TaintToleration count pass; KSG_WIN_COUNT with extensions is
+  // ServiceAntiAffinity with the extension filters (round 6: taints only, no extension scores, no
+  // extended-resource requests in the batch; use_window); any other mode scores as KSG_WIN_PLAIN
+  const int m = mode == KSG_WIN_COUNT || mode == KSG_WIN_ANTI || (ext && mode == KSG_WIN_TMAX) ? mode : KSG_WIN_PLAIN;
+#define KSG_EVAL_LAUNCH(M, G, X)                                                                                    \
+  hipLaunchKernelGGL((ksg_win_score_kernel<M, G, X>), grid, dim3(KSG_SC_NT), 0, st, d, batch, ids, run, wcap, sums, \
+                     wbits, wmax, ostride, dcnt, wfit, dmb, wbz, dz, exts, tmax, psoft, thist)
+#define KSG_EVAL_CASE(M, X)                             \
+  if (m == M && ext == X) {                             \
+    if (small) KSG_EVAL_LAUNCH(M, KSG_PG_SMALL, X);     \
+    else KSG_EVAL_LAUNCH(M, KSG_PG_LARGE, X);           \
   }
+  KSG_EVAL_CASE(KSG_WIN_TMAX, true)
+  KSG_EVAL_CASE(KSG_WIN_COUNT, true)
+  KSG_EVAL_CASE(KSG_WIN_ANTI, true)
+  KSG_EVAL_CASE(KSG_WIN_PLAIN, true)
+  KSG_EVAL_CASE(KSG_WIN_COUNT, false)
+  KSG_EVAL_CASE(KSG_WIN_ANTI, false)
+  KSG_EVAL_CASE(KSG_WIN_PLAIN, false)
+#undef KSG_EVAL_CASE
 #undef KSG_EVAL_LAUNCH
-#undef KSG_EVAL_LAUNCH_X
   return hipGetLastError();
 }
 
@@ -2780,7 +2590,7 @@ uint32_t ksg_win_max_window(const KsgDev& d) {
     const uint32_t mid = (lo + hi + 1) / 2;
     const uint32_t need = (anti && d.rr_dz && !(d.dbg & 4096))
                               ? win2_lds_offsets(P, nflag, mid, d.rr_dz, d.n_services).total
-                          : anti ? win_lds_offsets(P, nflag, mid, d.n_anti > 0, d.rr_dz, d.n_services).total
+                          : anti ? win_lds_offsets(P, nflag, mid, d.rr_dz, d.n_services).total
                                  : ksg_win_plain_lds(d, mid);
     if (need <= kWinLdsBudget) lo = mid;
     else hi = mid - 1;
@@ -2788,35 +2598,19 @@ uint32_t ksg_win_max_window(const KsgDev& d) {
   return lo;
 }
 
-template <int PP, bool ST, bool AN>
+// kernel: an instantiation of one of the two resolvers above
+template <auto kernel>
 static hipError_t win_resolve_launch(const KsgDev& d, uint32_t wcap, size_t lds, KsgWinRun* run,
                                      const KsgWinSum* sums, const KsgWinXchg& x, uint64_t* rng, int32_t* out,
                                      hipStream_t st) {
   static bool once = false;
   if (!once) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ksg_win_resolve_kernel<PP, ST, AN>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024);
     (void)hipGetLastError();  // do not leave a sticky error behind
     once = true;
   }
-  hipLaunchKernelGGL((ksg_win_resolve_kernel<PP, ST, AN>), dim3(1), dim3(win_res_nt(PP)), lds, st, d, wcap, run, sums, x,
-                     rng, out);
-  return hipGetLastError();
-}
-
-template <int PP, bool ST, bool AN>
-static hipError_t win_resolve2_launch(const KsgDev& d, uint32_t wcap, size_t lds, KsgWinRun* run,
-                                      const KsgWinSum* sums, const KsgWinXchg& x, uint64_t* rng, int32_t* out,
-                                      hipStream_t st) {
-  static bool once = false;
-  if (!once) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ksg_win_resolve2_kernel<PP, ST, AN>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipGetLastError();
-    once = true;
-  }
-  hipLaunchKernelGGL((ksg_win_resolve2_kernel<PP, ST, AN>), dim3(1), dim3(512), lds, st, d, wcap, run, sums, x, rng,
-                     out);
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(KSG_RES_NT), lds, st, d, wcap, run, sums, x, rng, out);
   return hipGetLastError();
 }
 
@@ -2825,40 +2619,26 @@ hipError_t ksg_launch_win_resolve(const KsgDev& d, uint32_t wcap, KsgWinRun* run
   const uint32_t P = win_P(d);
   if (x.fit_off == 0)  // no ServiceAntiAffinity: the plain resolver (ksg_plain.hip)
     return ksg_launch_win_plain(d, P, wcap, run, sums, x, rng, out, st);
-  if (x.fit_off != 0 && x.rr && !(d.dbg & 4096)) {
-    // ServiceAntiAffinity with the re-rank: the register-slot resolver
-    // (KSG_DEBUG & 4096: the LDS-slot resolver instead, for comparison)
-    const size_t lds2 = win2_lds_offsets(P, (d.n_services + 31) / 32, wcap, x.dz, d.n_services, 1).total;
-    // the debug instantiation: stamps (KSG_DEBUG & 8) or skews (bits 16..19)
-    const bool stamp2 = (d.dbg & 8) != 0 || ((uint32_t)d.dbg & 0x000f0000u) != 0;
-#define KSG_RES2A_CASE(PP)                                                                        \
-  if (P == PP)                                                                                    \
-    return stamp2 ? win_resolve2_launch<PP, true, true>(d, wcap, lds2, run, sums, x, rng, out, st) \
-                  : win_resolve2_launch<PP, false, true>(d, wcap, lds2, run, sums, x, rng, out, st);
-    KSG_RES2A_CASE(1)
-    KSG_RES2A_CASE(2)
-    KSG_RES2A_CASE(4)
-    KSG_RES2A_CASE(8)
-    KSG_RES2A_CASE(16)
-    KSG_RES2A_CASE(32)
-#undef KSG_RES2A_CASE
-    return hipErrorInvalidValue;
-  }
-  const size_t lds =
-      win_lds_offsets(P, (d.n_services + 31) / 32, wcap, x.fit_off != 0, x.rr ? x.dz : 0u, d.n_services).total;
+  // ServiceAntiAffinity with the re-rank: the register-slot resolver
+  // (KSG_DEBUG & 4096: the LDS-slot resolver instead, for comparison)
+  const bool reg = x.rr && !(d.dbg & 4096);
+  const uint32_t nflag = (d.n_services + 31) / 32;
+  const size_t lds = reg ? win2_lds_offsets(P, nflag, wcap, x.dz, d.n_services).total
+                         : win_lds_offsets(P, nflag, wcap, x.rr ? x.dz : 0u, d.n_services).total;
   // the debug instantiation: stamps (KSG_DEBUG & 8) or skews (bits 16..19)
   const bool stamp = (d.dbg & 8) != 0 || ((uint32_t)d.dbg & KSG_DBG_SKEW_MASK) != 0;
-  const bool anti = x.fit_off != 0;
-#define KSG_RES_CASE(PP, AN)                                                                          \
-  if (P == PP && anti == AN)                                                                          \
-    return stamp ? win_resolve_launch<PP, true, AN>(d, wcap, lds, run, sums, x, rng, out, st)         \
-                 : win_resolve_launch<PP, false, AN>(d, wcap, lds, run, sums, x, rng, out, st);
-  KSG_RES_CASE(1, true)
-  KSG_RES_CASE(2, true)
-  KSG_RES_CASE(4, true)
-  KSG_RES_CASE(8, true)
-  KSG_RES_CASE(16, true)
-  KSG_RES_CASE(32, true)
+#define KSG_RES_CASE(K, PP)                                                              \
+  if (P == PP)                                                                           \
+    return stamp ? win_resolve_launch<K<PP, true>>(d, wcap, lds, run, sums, x, rng, out, st) \
+                 : win_resolve_launch<K<PP, false>>(d, wcap, lds, run, sums, x, rng, out, st);
+#define KSG_RES_CASES(K) \
+  KSG_RES_CASE(K, 1) KSG_RES_CASE(K, 2) KSG_RES_CASE(K, 4) KSG_RES_CASE(K, 8) KSG_RES_CASE(K, 16) KSG_RES_CASE(K, 32)
+  if (reg) {
+    KSG_RES_CASES(ksg_win_resolve2_kernel)
+  } else {
+    KSG_RES_CASES(ksg_win_resolve_kernel)
+  }
+#undef KSG_RES_CASES
 #undef KSG_RES_CASE
   return hipErrorInvalidValue;
 }
