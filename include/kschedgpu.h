@@ -904,6 +904,77 @@ int ksg_headroom_batch(ksg_ctx* ctx, const ksg_pod* pods, const ksg_pod_ext* ext
  * on the context's stream (the copies out are not in it). Diagnostics. */
 int ksg_last_headroom_ms(ksg_ctx* ctx, double* ms);
 
+/* ---- First-fit pod sets: does a set of different pods fit together ----
+ * The drain, scale-down and gang-admission question ("if node x goes, do its pods all find
+ * room elsewhere", "do this driver and its workers fit now"), where a pod's placement changes
+ * what the next pod of the set sees: ksg_headroom_batch's total answers it for copies of one
+ * template only, and ksg_explain_batch judges every pod against the same state. Every set is
+ * packed on the device, independently and in parallel, without committing anything. The
+ * definition, in terms of ksg_explain_batch and ksg_add_pod, is the specification:
+ *   - Sets are independent: no set sees another set's placements. Set s owns the next
+ *     set_size[s] pods of the call; the sizes sum to n.
+ *   - For set s, start from the state AT THE TIME OF THE CALL. Its pods are p_0 .. p_{m-1}, in
+ *     the given order. For j = 0 .. m-1:
+ *     1. F is the nodes where ksg_explain_batch would report code 0 for p_j, with ext passed
+ *        the same way (ext == NULL skips the extension filters there too), less
+ *        set_exclude[s] and every node whose target_words bit is clear. Bits at or past
+ *        n_nodes are ignored.
+ *     2. If F is empty, out_nodes of p_j is KSG_OUT_NOFIT and the set goes on with p_{j+1}.
+ *     3. Otherwise t = the highest rank in F and out_nodes of p_j is t. Before p_{j+1} is
+ *        looked at, p_j counts as added to node t by ksg_add_pod / ksg_add_pod_ext under a
+ *        fresh uid.
+ *   - What counts as added: the pod's cpu, memory and extended-resource requests join the
+ *     node's totals with the reference's wrapping arithmetic (so a negative request makes
+ *     room), and every host port and GCE PD id it lists is held on t from then on, in the one
+ *     conflict-key id space: a key one pod lists as a port blocks a later pod that lists it as
+ *     a PD, as the keymap does.
+ *   - placed[s] is the number of pods of the set that found a node. The set fits iff
+ *     placed[s] == set_size[s]. A set of size 0 is legal: placed[s] is 0.
+ * First fit by descending rank is deterministic and cheap; it is a feasibility heuristic, as
+ * the cluster autoscaler's drain simulation is. A full placed[s] PROVES that a packing exists;
+ * a short one does NOT prove that none does. The caller's order is the heuristic's lever:
+ * largest pods first. Scores play no part, so HostName, LabelsPresence and the static terms,
+ * MatchNodeSelector and the taints are per (pod, node) constants; only NoDiskConflict,
+ * PodFitsPorts, PodFitsResources and the extended resources see the set's earlier pods.
+ * Invariants: with every set of size 1, no exclusion and no mask, out_nodes is
+ * ksg_preempt_batch's best_node with n_absent == 0; one set of k copies of a pod without ports
+ * or PDs and with non-negative requests fills the nodes, highest rank first, with
+ * ksg_headroom_batch's counts.
+ * ServiceAffinity: a set's first member can become the predicate's peer for the rest, which is
+ * not a per-node question (ksg_preempt_batch's reason). A context whose configuration has a
+ * ServiceAffinity predicate gets KSG_ERR_STATE (ksg_last_error says why), nothing written.
+ * Protocol and validation are the read-only queries'. ext[i] goes with pods[i], and uid is
+ * ignored. KSG_ERR_STATE while a ksg_schedule_begin is pending, or for ext on a context without
+ * extensions. KSG_NONODES for an empty node list (n_sets > 0). Every node is covered on every
+ * rank of a sharded context, with no exchange. n_sets == 0: KSG_OK, nothing written; n must
+ * then be 0. KSG_ERR_ARG, with nothing written: set_size NULL with n_sets > 0, sizes that do not
+ * sum to n, a size above KSG_PACK_MAX_SET, more than 2^31 - 1 sets (all sets go in one launch,
+ * one workgroup each), a set_exclude entry that is neither below n_nodes nor KSG_PACK_NO_NODE,
+ * out_nodes NULL with n > 0, placed NULL with n_sets > 0.
+ * The call changes nothing a later call can observe: not the committed totals, the keymap,
+ * the service tables, the generator state, the uid bookkeeping, the extended-resource usage or
+ * the results and the path of any later batch (like its siblings it does not look at the
+ * requests to decide between the int32 and the int64 score kernels).
+ * One workgroup packs one set, its pods one after another: the sets of a call run in parallel,
+ * one large set is serial work. All sets go in one launch, and no node count is too large: a
+ * set's own placements live in a table sized by KSG_PACK_MAX_SET, not by the cluster. A pod that
+ * lists host ports or GCE PDs, or requests an extended resource, also reads the records of the
+ * set's earlier such pods on every node the set has touched: quadratic in the pods of one set
+ * that pile onto a node, inside that one workgroup (unmeasured beyond the serial case). */
+#define KSG_PACK_NO_NODE 0xffffffffu
+#define KSG_PACK_MAX_SET 1024   /* pods per set */
+int ksg_pack_batch(ksg_ctx* ctx, const ksg_pod* pods, const ksg_pod_ext* ext /* NULL: all-zero */,
+                   uint32_t n, const uint32_t* ids, uint32_t n_ids,
+                   const uint32_t* set_size    /* n_sets; sums to n: set s owns the next set_size[s] pods */,
+                   const uint32_t* set_exclude /* n_sets node ranks or KSG_PACK_NO_NODE; NULL: none excluded */,
+                   uint32_t n_sets,
+                   const uint64_t* target_words /* optional, ceil(n_nodes/64): bit set = node may take pods */,
+                   int32_t* out_nodes /* n: node rank or KSG_OUT_NOFIT */,
+                   uint32_t* placed   /* n_sets: pods of the set that found a node */);
+/* Device time (ms) of the last ksg_pack_batch's kernel launch, from HIP events on the
+ * context's stream (the table upload and the copies out are not in it). Diagnostics. */
+int ksg_last_pack_ms(ksg_ctx* ctx, double* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -66,6 +66,8 @@ HEADROOM_ERR_PEER = 1
 HEADROOM_ERR_NEGATIVE = 2
 PREEMPT_MAX_VICTIMS = 256  # ksg_preempt_batch: the longest victim list written per pod
 PREEMPT_NOFIT = 0xFFFFFFFF  # ... node_victims where the node is not a candidate
+PACK_NO_NODE = 0xFFFFFFFF  # ksg_pack_batch: a set_exclude entry that excludes no node
+PACK_MAX_SET = 1024  # ... the most pods one set may hold
 
 MAX_ANTI = 64
 MAX_LABEL_PREF = 32
@@ -252,6 +254,8 @@ EXPORTS = [
     "ksg_update_cluster",
     "ksg_last_update_ms",
     "ksg_last_update_host_us",
+    "ksg_pack_batch",
+    "ksg_last_pack_ms",
 ]
 
 # int (*ksg_allgather_fn)(void* user, const void* send, void* recv, uint64_t bytes)
@@ -344,6 +348,9 @@ def load_library() -> C.CDLL:
         "ksg_update_cluster": (C.c_int, [vp, vp, U32, vp, U32, vp, U32, vp, vp, vp, U32, P(KsgNodeExtArrays)]),
         "ksg_last_update_ms": (C.c_int, [vp, P(C.c_double)]),
         "ksg_last_update_host_us": (C.c_int, [vp, vp]),
+        # (ctx, pods, ext | NULL, n, ids, n_ids, set_size, set_exclude | NULL, n_sets, target_words | NULL, out_nodes, placed)
+        "ksg_pack_batch": (C.c_int, [vp, vp, vp, U32, vp, U32, vp, vp, U32, vp, vp, vp]),
+        "ksg_last_pack_ms": (C.c_int, [vp, P(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

@@ -2,8 +2,8 @@
 // parts a node list determines (struct Cluster: the device tables and their geometry; struct
 // NodeMirror: the per-node half of the host mirror), the owning device-memory types (all
 // move-only), the error macros, the environment switches' parsers and the helpers
-// ksg_runtime.cpp defines and ksg_cluster.cpp, ksg_batch.cpp, ksg_without.cpp and
-// ksg_preempt.cpp call, among them the frame of the read-only batch queries (query_enter ...
+// ksg_runtime.cpp defines and ksg_cluster.cpp, ksg_batch.cpp, ksg_without.cpp, ksg_preempt.cpp
+// and ksg_pack.cpp call, among them the frame of the read-only batch queries (query_enter ...
 // query_chunks).
 #ifndef KSG_HOST_H_
 #define KSG_HOST_H_
@@ -307,6 +307,10 @@ struct ksg_ctx {
   DevBuf<uint32_t> d_vnode;
   size_t preempt_stage = (size_t)64 << 20;
   double last_preempt_ms = 0.0;
+  // ksg_pack_batch (ksg_pack.cpp): for the whole call int32 out_nodes[n], then uint32
+  // placed[n_sets] (one buffer, one copy out). Its tables share d_wtab / h_wtab too.
+  DevBuf<uint8_t> d_kout;
+  double last_pack_ms = 0.0;
   std::vector<KsgPatch> patches;
   // ksg_update_cluster: its remap kernels' device ms (ev0 .. ev1), and the call's host us:
   // validation, device (build, gather, patches, the wait), host mirror
@@ -491,7 +495,8 @@ int dalloc(ksg_ctx* c, DevBuf<T>& b, size_t count) {
 
 // ---- the read-only batch queries' frame -------------------------------------------
 // ksg_explain_batch, ksg_prioritize_batch, ksg_headroom_batch (ksg_runtime.cpp),
-// ksg_explain_without (ksg_without.cpp) and ksg_preempt_batch (ksg_preempt.cpp) answer for n pods against the device state as it
+// ksg_explain_without (ksg_without.cpp), ksg_preempt_batch (ksg_preempt.cpp) and ksg_pack_batch
+// (ksg_pack.cpp, whose unit is the pod set) answer for n pods against the device state as it
 // stands, in one or more launches over chunks of pods. Each is: its null-pointer check, the
 // lock, its own argument checks, then these steps in this order, with what only it does
 // (buffers, zeroing, tables, where the results land) in between. Every step returns a KSG_*

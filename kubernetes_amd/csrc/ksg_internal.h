@@ -296,6 +296,17 @@ struct KsgPreemptPart {
 };
 static_assert(sizeof(KsgPreemptPart) == 24, "KsgPreemptPart layout");
 
+// ksg_pack_kernel (ksg_pack.hip): one workgroup of KSG_PACK_STRIP threads per pod set scans the
+// nodes from the highest rank down in strips of KSG_PACK_STRIP / 64 bitmap words, one node per
+// lane; the first strip holds the last word, so nodes >= 64 * (nw - KSG_PACK_STRIP / 64). The
+// call's tables, built by ksg_pack.cpp:
+#define KSG_PACK_STRIP 256
+struct KsgPack {
+  const uint32_t* set_off;   // [n_sets + 1] set s owns the pods set_off[s] .. set_off[s + 1)
+  const uint32_t* exclude;   // [n_sets] a node rank no pod of the set may take, or KSG_PACK_NO_NODE; nullptr: none
+  const uint64_t* targets;   // [nw] bit set = the node may take pods; nullptr: every node
+};
+
 // ksg_headroom_kernel (ksg_headroom.hip) keeps that tiling
 #define KSG_HEADROOM_TILE KSG_EXPLAIN_TILE
 #define KSG_HEADROOM_CHUNK KSG_EXPLAIN_CHUNK

@@ -77,6 +77,10 @@ hipError_t ksg_launch_preempt(const KsgDev& d, const KsgWithout& w, const KsgPre
                               uint32_t* node_victims, KsgPreemptPart* part, int32_t* best_node, uint32_t* n_victims,
                               uint32_t* victims, uint32_t* cand_count, uint32_t* free_count, hipStream_t st);
 
+// ksg_pack.hip (one workgroup per set; out_nodes = int32[k.set_off[n_sets]], placed = uint32[n_sets])
+hipError_t ksg_launch_pack(const KsgDev& d, const KsgPack& k, const ksg_pod* pods, const ksg_pod_ext* exts,
+                           const uint32_t* ids, uint32_t n_sets, int32_t* out_nodes, uint32_t* placed, hipStream_t st);
+
 // ksg_headroom.hip (the per-pod arrays are indexed from `pods`; div: udiv_capped's variant)
 hipError_t ksg_launch_headroom(const KsgDev& d, const ksg_pod* pods, const ksg_pod_ext* exts, const uint32_t* ids,
                                uint32_t n_pods, uint32_t limit, int div, uint32_t* counts, uint64_t* total,

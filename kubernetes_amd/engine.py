@@ -424,6 +424,45 @@ class DeviceScheduler:
         self._lib.ksg_last_preempt_ms(self._ctx, C.byref(ms))
         return ms.value
 
+    def pack(self, batch: PodBatch, set_size, exclude=None, targets=None):
+        """ksg_pack_batch: do the pods of each set fit together. Set s owns the next set_size[s]
+        pods of `batch`; each pod in turn goes to the highest-rank node it fits on the committed
+        state plus the set's own earlier pods (their requests, host ports and GCE PDs), less
+        exclude[s] (a node rank, or abi.PACK_NO_NODE) and the nodes whose bit in `targets`
+        (uint64[ceil(N / 64)]) is clear. Sets do not see each other and nothing is committed.
+        First fit is a heuristic: a set that is placed whole fits, one that is not may still have
+        a packing in another order (largest pods first helps).
+        -> (out_nodes int32[n] (abi.KSG_OUT_NOFIT: no node), placed uint32[n_sets]). A
+        configuration with a ServiceAffinity predicate raises KsgError (KSG_ERR_STATE)."""
+        n = len(batch)
+        pods = np.ascontiguousarray(batch.pods, dtype=abi.POD_DTYPE)
+        ids = _u32(batch.ids if len(batch.ids) else np.zeros(1, np.uint32))
+        ext = None if batch.ext is None else np.ascontiguousarray(batch.ext, dtype=abi.POD_EXT_DTYPE)
+        sizes = _u32(set_size)
+        ns = len(sizes)
+        ex = None if exclude is None else _u32(exclude)
+        if ex is not None and len(ex) != ns:
+            raise ValueError(f"exclude has {len(ex)} entries for {ns} sets")
+        tw = None if targets is None else np.ascontiguousarray(targets, dtype=np.uint64)
+        if tw is not None and len(tw) != (self.n_nodes + 63) // 64:
+            raise ValueError(f"targets has {len(tw)} words for {self.n_nodes} nodes")
+        out = np.full(n, abi.KSG_OUT_NOFIT, np.int32)
+        placed = np.zeros(ns, np.uint32)
+        rc = self._lib.ksg_pack_batch(self._ctx, abi.ptr(pods) if n else None, abi.ptr(ext), n, abi.ptr(ids),
+                                      len(batch.ids), abi.ptr(sizes) if ns else None,
+                                      abi.ptr(ex) if ex is not None and ns else None, ns,
+                                      abi.ptr(tw) if tw is not None and len(tw) else None,
+                                      abi.ptr(out) if n else None, abi.ptr(placed) if ns else None)
+        if rc not in (abi.KSG_OK, abi.KSG_NONODES):
+            self._err(rc)
+        return out, placed
+
+    def last_pack_ms(self) -> float:
+        """Device ms of the last pack()'s kernel launch (HIP events)."""
+        ms = C.c_double(0)
+        self._lib.ksg_last_pack_ms(self._ctx, C.byref(ms))
+        return ms.value
+
     def prioritize(self, batch: PodBatch, top: int = 0, want_scores: bool = False):
         """ksg_prioritize_batch: filter and score every pod of `batch` against every node of the
         cluster as it stands, in one device pass, committing nothing.

@@ -21,7 +21,10 @@ O(events + assumed pods) on the host instead of O(all pods).
 """
 from __future__ import annotations
 
+import dataclasses
 from typing import Dict, List, Optional, Sequence
+
+import numpy as np
 
 from . import abi
 from .api import Node, Pod, Service
@@ -475,6 +478,77 @@ class GPUScheduler:
                 counts = {self.fail_names[c]: int(hist[j, c]) for c in range(1, hist.shape[1]) if hist[j, c]}
                 out[i] = FitError(pods[i], failed, counts)
         return out
+
+    # ---- dry run: do pod sets fit together ------------------------------------------------
+    def drainable(self, node_names: Sequence[str], minion_lister, movable=None) -> list:
+        """If node x goes, do its pods all find room elsewhere: one answer per name of
+        `node_names`, from one ksg_pack_batch. A node's set is the committed pods the device
+        holds on it, in uid order, without those `movable(pod)` says stay (DaemonSet-like pods),
+        as pending pods that are no longer pinned to a host. Each is placed first-fit on the
+        highest host that takes it given the set's earlier pods; the node itself is excluded,
+        and so is every other named node, so the answers for several nodes do not lean on each
+        other's room. Per node {"fits": every pod found a host, "moves": {namespace/name: host
+        name or None}}. First fit is a heuristic: fits=True proves that the node can be drained
+        now, fits=False does not prove that it cannot. Nothing is committed, drawn or assumed.
+        A KeyError for a name that is no node; NoMinionsError entries without nodes. Not
+        available under a ServiceAffinity predicate (KsgError)."""
+        nodes = minion_lister.list()
+        if len(nodes) == 0:
+            return [NoMinionsError() for _ in node_names]
+        self._sync(nodes)
+        if not node_names:
+            return []
+        names = self.view.names
+        rank = {n: i for i, n in enumerate(names)}
+        ranks = [rank[n] for n in node_names]
+        on = {r: [] for r in ranks}
+        for p, _ in self._committed():
+            r = rank.get(p.status.host)
+            if r in on and (movable is None or movable(p)):
+                on[r].append(p)
+        b = PodBatchBuilder(self.view, self.aff_labels)
+        sets = [on[r] for r in ranks]
+        for pods in sets:
+            for p in pods:
+                b.add(Pod(metadata=p.metadata, spec=dataclasses.replace(p.spec, host="")), 0)  # (uids are ignored)
+        targets = np.full((len(names) + 63) // 64, ~np.uint64(0), np.uint64)
+        for r in ranks:
+            targets[r >> 6] &= ~(np.uint64(1) << np.uint64(r & 63))
+        out, placed = self.engine.pack(b.build(), [len(s) for s in sets], exclude=ranks, targets=targets)
+        res, at = [], 0
+        for s, pods in enumerate(sets):
+            moves = {p.key(): (names[int(out[at + j])] if out[at + j] >= 0 else None) for j, p in enumerate(pods)}
+            res.append({"fits": int(placed[s]) == len(pods), "moves": moves})
+            at += len(pods)
+        return res
+
+    def fits_together(self, gangs: Sequence[Sequence[Pod]], minion_lister) -> list:
+        """Does each gang of pending pods (a driver and its workers, a pod group with a port or a
+        PD per member) fit as a whole now: per gang {"fits": bool, "hosts": [host name or None per
+        pod]}, from one ksg_pack_batch. The pods of a gang are placed in the given order, first
+        fit on the highest host, each seeing the requests, host ports and GCE PDs of the gang's
+        earlier pods; gangs do not see each other. First fit is a heuristic: fits=True proves that
+        the gang fits, fits=False does not prove that it cannot (largest pods first helps).
+        Nothing is committed, drawn or assumed. NoMinionsError entries without nodes. Not
+        available under a ServiceAffinity predicate (KsgError)."""
+        nodes = minion_lister.list()
+        if len(nodes) == 0:
+            return [NoMinionsError() for _ in gangs]
+        self._sync(nodes)
+        if not gangs:
+            return []
+        b = PodBatchBuilder(self.view, self.aff_labels)
+        for g in gangs:
+            for p in g:
+                b.add(p, 0)  # (the call ignores uids)
+        out, placed = self.engine.pack(b.build(), [len(g) for g in gangs])
+        names = self.view.names
+        res, at = [], 0
+        for s, g in enumerate(gangs):
+            hosts = [names[int(o)] if o >= 0 else None for o in out[at: at + len(g)]]
+            res.append({"fits": int(placed[s]) == len(g), "hosts": hosts})
+            at += len(g)
+        return res
 
 
 def new_gpu_scheduler(config: SchedulerConfig, pod_lister, service_lister=None, random=None,
