@@ -11,7 +11,7 @@
 //   batch_publish    the deferred replay and the totals                 (7)
 //
 // The context, the scratch buffers and the helpers shared with the rest of the runtime
-// (ksg_runtime.cpp) are in ksg_host.h.
+// (ksg_runtime.cpp; srv_stop is ksg_dropin.cpp's) are in ksg_host.h.
 #include <cmath>
 #include <cstring>
 
@@ -381,11 +381,11 @@ int win_enqueue_round(ksg_ctx* c, const WinPlan& pl, uint32_t pos, uint32_t n, u
   int rc;
   const KsgWinXchg& x = pl.x;
   const uint32_t W = pl.W;
-  KsgWinRun* const fruns = reinterpret_cast<KsgWinRun*>(c->d_fctl);
+  KsgWinRun* const fruns = reinterpret_cast<KsgWinRun*>(c->d_fctl.p);
   uint32_t* const fcnt = reinterpret_cast<uint32_t*>(c->d_fctl + kFctlRuns);
   *c->h_run = KsgWinRun{pos, n, 0, 0, {0, 0, 0, 0}};
   if (pl.fused) {  // slot 0 and both counter sets (the launches zero the next set as they go)
-    *reinterpret_cast<KsgWinRun*>(c->h_fctl) = *c->h_run;
+    *reinterpret_cast<KsgWinRun*>(c->h_fctl.p) = *c->h_run;
     HIPCHK(c, hipMemcpyAsync(c->d_fctl, c->h_fctl, kFctlRuns + (size_t)2 * pl.fgroups * 8 * sizeof(uint32_t),
                              hipMemcpyHostToDevice, c->st));
   } else {
@@ -509,8 +509,8 @@ int win_rounds(ksg_ctx* c, const WinPlan& pl, BatchRun& run) {
   while (pos < n) {
     if (c->wev.size() < 3 * (size_t)K + 1) {
       const size_t old = c->wev.size();
-      c->wev.resize(3 * (size_t)K + 1, nullptr);
-      for (size_t i = old; i < c->wev.size(); ++i) HIPCHK(c, hipEventCreateWithFlags(&c->wev[i], kTimingEvent));
+      c->wev.resize(3 * (size_t)K + 1);
+      for (size_t i = old; i < c->wev.size(); ++i) HIPCHK(c, hipEventCreateWithFlags(&c->wev[i].e, kTimingEvent));
     }
     // the sampled launches rotate from round to round (launches k with
     // (k + ev_off) % es == 0), so every position in a round, the no-op
@@ -583,7 +583,7 @@ int ksg_schedule_batch(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint32
                        uint64_t* rng_state, int32_t* out_nodes) {
   if (!c || (n && (!pods || !out_nodes)) || !rng_state) return KSG_ERR_ARG;
   KSG_LOCK(c);
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
+  if (c->pb.on) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
   if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
   if (int rs = cluster_ok(c)) return rs;
   HIPCHK(c, hipSetDevice(c->device));
@@ -629,7 +629,7 @@ int ksg_schedule_batch_draws(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const 
   for (uint32_t k = 0; k < n; ++k)
     if (draws[k] > (uint64_t)INT64_MAX) return fail(c, KSG_ERR_ARG, "draw %u is not a rand.Int() value", k);
   *draws_used = 0;
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
+  if (c->pb.on) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
   if (n == 0) return ksg_schedule_batch(c, pods, 0, ids, n_ids, &c->draw_tmp, out_nodes);
   HIPCHK(c, hipSetDevice(c->device));
   if (int rs_ = srv_stop(c)) return rs_;
@@ -652,7 +652,7 @@ int ksg_batch_unwind(ksg_ctx* c, const ksg_pod* pods, const int32_t* out_nodes, 
                      uint64_t* rng_state, uint32_t* draws_kept) {
   if (!c || !pods || !out_nodes || !draws_kept || k >= n) return KSG_ERR_ARG;
   KSG_LOCK(c);
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
+  if (c->pb.on) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
   if (out_nodes[k] < 0) return fail(c, KSG_ERR_ARG, "pod %u found no node: there was no Bind to reject", k);
   if (int rs = cluster_ok(c)) return rs;
   HIPCHK(c, hipSetDevice(c->device));

@@ -1,8 +1,8 @@
 // ksg_cluster.cpp — the node list: ksg_set_cluster and ksg_update_cluster with the builder they
 // share (build_cluster fills the context's Cluster, ksg_host.h), the static terms folded into a
 // list afterwards (ksg_set_static_terms, ksg_add_static_config) and the node extensions
-// (ksg_set_node_ext, ksg_read_ext_used). The helpers it calls are ksg_runtime.cpp's, declared in
-// ksg_host.h.
+// (ksg_set_node_ext, ksg_read_ext_used). The helpers it calls are ksg_runtime.cpp's (srv_stop: ksg_dropin.cpp's),
+// declared in ksg_host.h.
 #include <cmath>
 #include <cstring>
 
@@ -307,7 +307,7 @@ int ksg_set_static_terms(ksg_ctx* c, const uint64_t* fit_words, const int64_t* s
   if (!c || (!fit_words && !score)) return KSG_ERR_ARG;
   KSG_LOCK(c);
   if (int rs = cluster_ok(c)) return rs;
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
+  if (c->pb.on) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
   // (a node failing the extra fit words reports KSG_FAIL_LABELSPRESENCE: the config must name it)
   if (fit_words && !(c->cfg.predicates & KSG_PRED_LABELSPRESENCE))
     return fail(c, KSG_ERR_ARG, "ksg_set_static_terms: fit words need KSG_PRED_LABELSPRESENCE in the config");
@@ -348,7 +348,7 @@ int ksg_add_static_config(ksg_ctx* c, const ksg_config* extra) {
   if (!c || !extra) return KSG_ERR_ARG;
   KSG_LOCK(c);
   if (int rs = cluster_ok(c)) return rs;
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
+  if (c->pb.on) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
   if (extra->n_presence > KSG_MAX_PRESENCE || extra->n_label_pref > KSG_MAX_LABEL_PREF)
     return fail(c, KSG_ERR_ARG, "ksg_add_static_config: more terms than the config's slots");
   for (uint32_t q = 0; q < extra->n_presence; ++q)
@@ -415,7 +415,7 @@ int ksg_set_node_ext(ksg_ctx* c, uint32_t n_nodes, const int64_t* scalar_cap, co
                      const uint32_t* taint_n, const uint32_t* taint_ids, uint32_t n_taint_ids) {
   if (!c) return KSG_ERR_ARG;
   KSG_LOCK(c);
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
+  if (c->pb.on) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
   if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
   if (!c->ext_on) return fail(c, KSG_ERR_STATE, "ksg_set_node_ext: extensions are off");
   if (!c->have_cluster || n_nodes != c->cl.N) return fail(c, KSG_ERR_ARG, "ksg_set_node_ext: node count != cluster");
@@ -527,7 +527,7 @@ static int update_cluster_impl(ksg_ctx* c, const ksg_node* nodes, uint32_t n_nod
                                uint32_t n_outside, const ksg_node_ext_arrays* ext) {
   const auto t0 = std::chrono::steady_clock::now();
   if (int rs = cluster_ok(c)) return rs;
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
+  if (c->pb.on) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
   if (ext && !c->ext_on) return fail(c, KSG_ERR_STATE, "ksg_update_cluster: ext given, extensions are off");
   if (!ext && c->ext_on) return fail(c, KSG_ERR_ARG, "ksg_update_cluster: extensions are on, ext == NULL");
   // (what the arguments alone decide comes first: such a refusal does not even stop the server)

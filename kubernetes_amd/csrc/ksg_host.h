@@ -1,10 +1,11 @@
-// ksg_host.h — what the host translation units share: the context (struct ksg_ctx) with the two
-// parts a node list determines (struct Cluster: the device tables and their geometry; struct
-// NodeMirror: the per-node half of the host mirror), the owning device-memory types (all
-// move-only), the error macros, the environment switches' parsers and the helpers
-// ksg_runtime.cpp defines and ksg_cluster.cpp, ksg_batch.cpp, ksg_without.cpp, ksg_preempt.cpp
-// and ksg_pack.cpp call, among them the frame of the read-only batch queries (query_enter ...
-// query_chunks).
+// ksg_host.h — what the host translation units share: the error macros, the environment
+// switches' parsers, the owning types (device and pinned memory, stream, event, communicator;
+// none can be copied), the context (struct ksg_ctx) and its named parts (struct Cluster and struct
+// NodeMirror: what a node list determines; struct SrvClient: the resident server's host state;
+// struct PendingBegin: the pod between begin and commit), and the functions one host file
+// defines and another calls: ksg_runtime.cpp's helpers, the little ksg_dropin.cpp shows of the
+// server's client, ksg_query.cpp's frame of the read-only batch queries (query_enter ...
+// query_chunks) and ksg_without.cpp's table builder.
 #ifndef KSG_HOST_H_
 #define KSG_HOST_H_
 
@@ -98,29 +99,84 @@ struct DevBuf {
   }
 };
 
-// Pinned host staging of `cap` bytes: max(need, 2 x cap, 4096) (geometric: a pinned
-// (re)allocation costs ~0.2 ms, hipHostFree synchronises)
-struct HostBuf {
-  uint8_t* p = nullptr;
+// Pinned host memory of `cap` elements, allocated with `flags`, that frees itself with the
+// context; dp is its device address where the device writes it (any flags but the default:
+// the coherent and the mapped allocations). alloc() replaces it with exactly `count` elements,
+// contents dropped; grow() is the staging policy: max(need, 2 x cap, 4096) (geometric: a
+// pinned (re)allocation costs ~0.2 ms, hipHostFree synchronises). Stays where it is declared.
+template <typename T>
+struct Pinned {
+  T* p = nullptr;
+  T* dp = nullptr;
   size_t cap = 0;
-  HostBuf() = default;
-  HostBuf(const HostBuf&) = delete;
-  HostBuf& operator=(const HostBuf&) = delete;
-  ~HostBuf() {
+  const unsigned flags;
+  explicit Pinned(unsigned flags_ = hipHostMallocDefault) : flags(flags_) {}
+  Pinned(const Pinned&) = delete;
+  Pinned& operator=(const Pinned&) = delete;
+  ~Pinned() {
     if (p) (void)hipHostFree(p);
   }
-  operator uint8_t*() const { return p; }
-  int grow(ksg_ctx* c, size_t need) {
-    if (cap >= need) return KSG_OK;
-    const size_t nc = std::max<size_t>(need, std::max<size_t>(cap * 2, 4096));
+  operator T*() const { return p; }
+  T* operator->() const { return p; }
+  int alloc(ksg_ctx* c, size_t count) {
     if (p) (void)hipHostFree(p);
-    p = nullptr;
+    p = dp = nullptr;
     cap = 0;
-    HIPCHK(c, hipHostMalloc((void**)&p, nc, hipHostMallocDefault));
-    cap = nc;
+    HIPCHK(c, hipHostMalloc((void**)&p, count * sizeof(T), flags));
+    cap = count;
+    if (flags != hipHostMallocDefault && hipHostGetDevicePointer((void**)&dp, p, 0) != hipSuccess) {
+      (void)hipHostFree(p);
+      p = dp = nullptr;
+      cap = 0;
+      return fail(c, KSG_ERR_HIP, "hipHostGetDevicePointer failed");
+    }
     return KSG_OK;
   }
+  int grow(ksg_ctx* c, size_t need) {
+    return cap >= need ? KSG_OK : alloc(c, std::max<size_t>(need, std::max<size_t>(cap * 2, 4096)));
+  }
 };
+using HostBuf = Pinned<uint8_t>;  // the staging buffers, in bytes
+
+// A HIP stream, a HIP event and the RCCL communicator, each destroyed with its owner while
+// the owner's device is current. The stream and the communicator stay where they are
+// declared; an event moves (the window path keeps a growing vector of them).
+struct Stream {
+  hipStream_t s = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  ~Stream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+  operator hipStream_t() const { return s; }
+};
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+  Event& operator=(Event&& o) noexcept {
+    std::swap(e, o.e);
+    return *this;
+  }
+  ~Event() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  operator hipEvent_t() const { return e; }
+};
+struct Comm {
+  ncclComm_t c = nullptr;
+  Comm() = default;
+  Comm(const Comm&) = delete;
+  Comm& operator=(const Comm&) = delete;
+  ~Comm() {
+    if (c) (void)ncclCommDestroy(c);
+  }
+  operator ncclComm_t() const { return c; }
+};
+static_assert(!std::is_copy_constructible<HostBuf>::value && !std::is_copy_constructible<Stream>::value &&
+                  !std::is_copy_constructible<Event>::value && !std::is_copy_constructible<Comm>::value,
+              "the owners of pinned memory, streams, events and the communicator are not copied");
 
 // The fixed-size device arrays of one node list (dalloc adds them), freed with their owner.
 // Move-only; a moved-from owner holds none.
@@ -220,13 +276,73 @@ struct NodeMirror {
         svc_max(S, 0), svc_total(S, 0), svc_peer(S, -1), svc_members(S) {}
 };
 
+// The host's side of the resident drop-in server (ksg_serve.hip; the client is ksg_dropin.cpp):
+// begin / commit as requests in mapped host memory instead of launches, copies and stream
+// syncs. The context holds one (c->srv), which owns the request block, the fail codes and the
+// grid server's device state. As constructed: the KSG_SERVE* switches read, nothing allocated,
+// no server running.
+struct SrvClient {
+  bool enabled = true;       // KSG_SERVE=0: the launch-per-call path
+  bool running = false;      // a server kernel may be resident on the context's stream
+  Pinned<KsgSrvBox> box{hipHostMallocCoherent | hipHostMallocMapped};  // the request / response block
+  Pinned<uint8_t> fail{hipHostMallocCoherent | hipHostMallocMapped};   // fail codes of the shard's nodes
+  DevBuf<KsgSrvGrid> grid;   // the grid server's device state
+  uint32_t seq = 0;          // last request posted
+  uint64_t idle_us = 20000;  // KSG_SERVE_IDLE_US: the server returns after this long without a request
+  uint32_t unacked = 0;      // a COMMIT posted without waiting for its answer (0: none)
+  uint32_t served = 0;       // every request up to this one was served
+  uint32_t last_ctl = 0;     // the last control request posted
+  uint64_t launches = 0;
+  bool grid_on = true;       // KSG_SERVE_GRID=0: the one-workgroup server at every size
+  uint32_t npt4_min = 16384;  // KSG_SERVE_GRID_NPT4_MIN: past this many nodes 4 nodes per thread
+  // KSG_SERVE_GRID_MIN: shards above this many nodes take the grid server
+  // (it beats the one-workgroup server at 500 nodes already: 7.2 vs 10.9 us)
+  uint32_t grid_min = 0;
+  bool grid_ext = true;      // KSG_SERVE_GRID_EXT=0: extension contexts on the one-workgroup server
+  uint32_t epoch = 0;
+  int64_t grid_opts = -1;    // KSG_SERVE_GRID_OPTS (KsgSrvArgs.grid_opts; -1: by size)
+  bool stamps = false;       // KSG_SERVE_STAMPS=1: sum the server's per-stage cycles of each begin
+  bool debug = false;        // KSG_SERVE_DEBUG=1: the grid server's stage markers, reported on a fault
+  bool trace = false;        // KSG_SERVE_TRACE=1: every post, wait and relaunch to stderr
+  double stage[6] = {};      // (printed by srv_print_stamps)
+  uint64_t stamped = 0;
+  SrvClient();
+};
+
+// The pod between ksg_schedule_begin and its commit (c->pb). clear() ends it: at the commit,
+// when the next begin abandons it, and when ksg_set_cluster resets the mirror.
+struct PendingBegin {
+  bool on = false;
+  uint64_t k = 0;  // its tie count
+  ksg_pod pod{};
+  std::vector<uint32_t> ids;
+  bool served = false;       // by the resident server: the commit picks the node on the host, from
+  std::vector<uint64_t> tw;  // ... the begin's tie words (node lo + 64 i + b)
+  bool ext_on = false;       // ... and carries the begin's extension record
+  ksg_pod_ext ext{};
+  PendingBegin() = default;
+  PendingBegin(const PendingBegin&) = delete;
+  PendingBegin& operator=(const PendingBegin&) = delete;
+  void clear() {
+    on = served = ext_on = false;
+    k = 0;
+    pod.uid = ~0ULL;
+    ids.clear();
+    tw.clear();
+  }
+};
+static_assert(!std::is_copy_constructible<SrvClient>::value && !std::is_copy_constructible<PendingBegin>::value,
+              "the server's client and the pending begin stay in their context");
+
 #pragma GCC visibility pop
 
 struct ksg_ctx {
   ksg_config cfg{};
   int device = 0, rank = 0, world = 1;
-  hipStream_t st = nullptr;
-  ncclComm_t comm = nullptr;
+  // Declared before everything that is freed, so destroyed after it: members go in reverse
+  // order, and hipFree / hipHostFree of memory the stream's work used come before the stream's end.
+  Stream st;
+  Comm comm;
   bool xchg = false;  // exchange path: world > 1, or a 1-rank RCCL communicator
   double ppw_est = 0.0;  // pods resolved per window (window path round sizing)
   // windows per round = margin x (pods left) / ppw_est + 1 (KSG_ROUND_MARGIN): the
@@ -239,9 +355,9 @@ struct ksg_ctx {
   ksg_allgather_fn xfn = nullptr;
   void* xuser = nullptr;
   HostBuf h_xsend, h_xrecv;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  Event ev0, ev1;
   // the batch path's waits spin on this event (KSG_SPIN_WAIT=0: hipStreamSynchronize)
-  hipEvent_t ev_wait = nullptr;
+  Event ev_wait;
   bool spin_wait = true;
   double last_ms = 0.0;
   std::string err;
@@ -266,8 +382,7 @@ struct ksg_ctx {
   DevBuf<uint8_t> d_one;
   const ksg_pod* one_pod = nullptr;
   const uint32_t* one_ids = nullptr;
-  uint8_t* h_map = nullptr;  // pinned, coherent: [0, 32) summary int64[3], [32, 36) node
-  uint8_t* d_map = nullptr;  // its device address
+  Pinned<uint8_t> h_map{hipHostMallocCoherent};  // [0, 32) summary int64[3], [32, 36) node (the device writes h_map.dp)
   DevBuf<KsgPatch> d_patch;
   DevBuf<uint64_t> d_draws;  // ksg_schedule_batch_draws: the caller's rand.Int() values
   uint64_t draw_tmp = 0;
@@ -275,7 +390,7 @@ struct ksg_ctx {
   // ksg_explain_batch: the per-node codes of one chunk of pods (bounded: kExplainStageBytes),
   // the histograms uint32[n][KSG_EXPLAIN_SLOTS] then the error flags uint8[n] of the whole call
   DevBuf<uint8_t> d_xcodes, d_xhist;
-  hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr;  // around its kernel launches
+  Event ev_x0, ev_x1;  // around its kernel launches
   double last_explain_ms = 0.0;
   // ksg_prioritize_batch, per chunk of pods (each bounded by kExplainStageBytes): the per-node
   // scores; the normalised terms int32[per][D + 1], the tile partials and their candidates
@@ -344,9 +459,9 @@ struct ksg_ctx {
   DevBuf<int32_t> d_ethist;   // [W][KSG_TBINS] ... the histogram of its soft-taint counts
   DevBuf<uint64_t> d_epsoft;  // [W] ... the pods' untolerated soft taints as masks
   DevBuf<KsgWinRun> d_run;         // progress of the window chain (device)
-  KsgWinRun* h_run = nullptr;      // pinned host copy
+  Pinned<KsgWinRun> h_run;         // pinned host copy
   uint32_t last_stats[4] = {0, 0, 0, 0};  // windows, stops (service scalar), stops (ties exhausted)
-  std::vector<hipEvent_t> wev;     // event pairs around the chained window kernels
+  std::vector<Event> wev;          // event pairs around the chained window kernels
   double last_kms[3] = {0, 0, 0};  // phase A ms, phase B ms, launches (window path)
   double last_t0ms = 0;            // ... and between them: the exchange (sharded) and the T0 images
   double last_wsum = 0;            // window capacity W summed over the launches
@@ -360,8 +475,8 @@ struct ksg_ctx {
   // latency (config 5, 100k nodes, same box: 255k fused against 385k apart; 45k nodes: 492k fused
   // against 465k, profiles/r6_fused_threshold.json)
   uint32_t fused_max_words = 1024;
-  uint8_t* d_fctl = nullptr;        // KsgWinRun[2], then the counters uint32[2][groups][8]
-  uint8_t* h_fctl = nullptr;        // pinned: the round's first slot and zeroed counters
+  DevBuf<uint8_t> d_fctl;           // KsgWinRun[2], then the counters uint32[2][groups][8]
+  HostBuf h_fctl;                   // pinned: the round's first slot and zeroed counters
   double last_hus[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // host us per phase of the last batch (ksg_last_batch_host_us)
   double totals[24] = {};  // ksg_batch_totals: the per-batch diagnostics summed over batches
 
@@ -385,47 +500,8 @@ struct ksg_ctx {
   DevBuf<ksg_pod_ext> d_pext;            // device copy (batch / explain)
   ksg_pod_ext* d_one_ext = nullptr;      // the single pod's record (inside d_one)
 
-  // the resident drop-in server (ksg_serve.hip): begin / commit as requests in
-  // mapped host memory instead of launches, copies and stream syncs
-  bool srv_enabled = true;      // KSG_SERVE=0: the launch-per-call path
-  bool srv_running = false;     // a server kernel may be resident on `st`
-  KsgSrvBox* srv_box = nullptr;   // pinned, coherent, mapped
-  KsgSrvBox* srv_dbox = nullptr;  // its device address
-  uint8_t* srv_fail = nullptr;    // fail codes of the shard's nodes (mapped)
-  uint8_t* srv_dfail = nullptr;
-  size_t srv_fail_cap = 0;
-  uint32_t srv_seq = 0;         // last request posted
-  uint64_t srv_idle_us = 20000; // the server returns after this long without a request
-  bool pend_srv = false;        // the pending begin was served by the server
-  uint32_t srv_bhdr[KSG_SRV_HDR_DW] = {};  // that begin's header (its payload layout)
-  std::vector<uint64_t> srv_tw;  // its tie words (node lo + 64 i + b), the commit picks from them
-  uint32_t srv_unacked = 0;      // a COMMIT posted without waiting for its answer (0: none)
-  uint32_t srv_served = 0;       // every request up to this one was served
-  uint32_t srv_last_ctl = 0;     // the last control request posted
-  bool srv_pext_on = false;      // the pending begin's extension record (its commit carries it)
-  ksg_pod_ext srv_pext{};
-  uint64_t srv_launches = 0;
-  bool srv_grid_on = true;       // KSG_SERVE_GRID=0: the one-workgroup server at every size
-  uint32_t srv_npt4_min = 16384;  // KSG_SERVE_GRID_NPT4_MIN: past this many nodes 4 nodes per thread
-  // KSG_SERVE_GRID_MIN: shards above this many nodes take the grid server
-  // (it beats the one-workgroup server at 500 nodes already: 7.2 vs 10.9 us)
-  uint32_t srv_grid_min = 0;
-  bool srv_grid_ext = true;  // KSG_SERVE_GRID_EXT=0: extension contexts on the one-workgroup server
-  KsgSrvGrid* srv_grid = nullptr;  // its device state (+ the fail codes)
-  size_t srv_grid_cap = 0;
-  uint32_t srv_epoch = 0;
-  bool srv_stamps = false;      // KSG_SERVE_STAMPS=1: sum the server's per-stage cycles of each begin
-  int64_t srv_grid_opts = -1;   // KSG_SERVE_GRID_OPTS (KsgSrvArgs.grid_opts; -1: by size)
-  bool srv_debug = false;       // KSG_SERVE_DEBUG=1: the grid server's stage markers, reported on a fault
-  bool srv_trace = false;       // KSG_SERVE_TRACE=1: every post, wait and relaunch to stderr
-  double srv_stage[6] = {};     // (printed by ksg_destroy)
-  uint64_t srv_stamped = 0;
-
-  // begin/commit
-  bool pending = false;
-  uint64_t pending_k = 0;
-  ksg_pod pend{};
-  std::vector<uint32_t> pend_ids;
+  SrvClient srv;    // the resident drop-in server's client (ksg_dropin.cpp)
+  PendingBegin pb;  // the begin that awaits its commit
 
   // Every entry point holds `mu`, so reflector threads may call ksg_add_pod /
   // ksg_remove_pod while the scheduling thread schedules. Updates that arrive
@@ -459,7 +535,8 @@ int flush_patches(ksg_ctx* c);
 int upload_pods(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint32_t* ids, size_t n_ids);
 int wait_device(ksg_ctx* c);
 int cluster_ok(ksg_ctx* c);
-int srv_stop(ksg_ctx* c);
+int mirror_add(ksg_ctx* c, uint32_t h, const ksg_pod* p, const uint32_t* ids, bool emit);
+size_t pod_ids_extent(const ksg_pod* p);
 int scan_exchange(ksg_ctx* c, const ksg_pod* dpod, const uint32_t* dids, int mode, uint8_t* fail_out,
                   int64_t* score_out, const ksg_pod_ext* dext);
 int allgather(ksg_ctx* c, const void* dsend, void* drecv, size_t bytes);
@@ -493,8 +570,15 @@ int dalloc(ksg_ctx* c, DevBuf<T>& b, size_t count) {
   return rc;
 }
 
-// ---- the read-only batch queries' frame -------------------------------------------
-// ksg_explain_batch, ksg_prioritize_batch, ksg_headroom_batch (ksg_runtime.cpp),
+// ---- the resident server's client (ksg_dropin.cpp), as far as the other files see it ------
+// Ends the resident server so other work can use the context's stream (every entry point that
+// enqueues on it calls this first); the next served begin launches it again.
+int srv_stop(ksg_ctx* c);
+int srv_flush_patches(ksg_ctx* c);  // flush_patches while a server is running: through its request block
+void srv_print_stamps(ksg_ctx* c);  // ksg_destroy: what KSG_SERVE_STAMPS=1 gathered, to stderr
+
+// ---- the read-only batch queries' frame (ksg_query.cpp) ---------------------------
+// ksg_explain_batch, ksg_prioritize_batch, ksg_headroom_batch (ksg_query.cpp),
 // ksg_explain_without (ksg_without.cpp), ksg_preempt_batch (ksg_preempt.cpp) and ksg_pack_batch
 // (ksg_pack.cpp, whose unit is the pod set) answer for n pods against the device state as it
 // stands, in one or more launches over chunks of pods. Each is: its null-pointer check, the
@@ -546,6 +630,7 @@ int without_tables(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint64_t* 
 int without_position(ksg_ctx* c, const uint32_t* first_absent, uint32_t i, uint32_t n_absent);
 extern "C" {  // (defined among the entry points, inside ksg_runtime.cpp's extern "C" block)
 int remove_pod_impl(ksg_ctx* c, uint64_t uid);
+int apply_queued(ksg_ctx* c);
 int note_ext(ksg_ctx* c, const ksg_pod* p, const ksg_pod_ext* e, size_t n_ids);
 int check_ext_range(ksg_ctx* c, const ksg_pod_ext* e, size_t n_ids);
 int check_taint_ids(ksg_ctx* c, const ksg_pod_ext* e, const uint32_t* ids);

@@ -1,10 +1,10 @@
-// ksg_runtime.cpp — host runtime of libkschedgpu.so: the C ABI in
-// include/kschedgpu.h except the batch entry points, the device-state mirror, the
-// RCCL exchange, the per-pod path (begin / commit / evaluate) with its resident
-// server, kubelet admission, the pods' extension records and ksg_explain_batch. The batch driver
-// (ksg_schedule_batch and its variants) is ksg_batch.cpp, the node list (ksg_set_cluster,
-// ksg_update_cluster, the static terms, the node extensions) ksg_cluster.cpp; ksg_host.h holds
-// what the files share (struct ksg_ctx, the scratch-buffer types, the helpers declared there).
+// ksg_runtime.cpp — host runtime of libkschedgpu.so: the context's lifetime (ksg_create*,
+// ksg_destroy), the device-state mirror with its patches, ksg_add_pod / ksg_remove_pod, the
+// RCCL exchange, the read-backs, kubelet admission, the pods' extension records, and the
+// helpers ksg_host.h declares for the other host files. Those are: the per-pod path (begin /
+// commit / evaluate) with the resident server's client, ksg_dropin.cpp; the read-only queries'
+// frame and the three oldest queries, ksg_query.cpp (the newer ones: ksg_without.cpp,
+// ksg_preempt.cpp, ksg_pack.cpp); the batch driver, ksg_batch.cpp; the node list, ksg_cluster.cpp.
 //
 // Reference behaviour mirrored here:
 //   genericScheduler.Schedule / selectHost     pkg/scheduler/generic_scheduler.go:54-96
@@ -40,9 +40,6 @@ int fail(ksg_ctx* c, int code, const char* fmt, ...) {
 // is exported from the library.
 #pragma GCC visibility push(hidden)
 
-// ksg_explain_batch: device staging for the per-node codes of one chunk of pods
-constexpr size_t kExplainStageBytes = (size_t)64 << 20;
-
 int pick_R(uint32_t shard_nodes) {
   const uint32_t r = (shard_nodes + KSG_NT - 1) / KSG_NT;
   int R = 1;
@@ -64,11 +61,9 @@ void patch_andnot(ksg_ctx* c, const void* addr, uint64_t v) {
   c->patches.push_back(KsgPatch{(uint64_t)(uintptr_t)addr, v, 3, 0});
 }
 
-int srv_flush_patches(ksg_ctx* c);
-
 int flush_patches(ksg_ctx* c) {
   if (c->patches.empty()) return KSG_OK;
-  if (c->srv_running) return srv_flush_patches(c);
+  if (c->srv.running) return srv_flush_patches(c);
   int rc = c->d_patch.grow(c, c->patches.size());
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(c->d_patch, c->patches.data(), c->patches.size() * sizeof(KsgPatch),
@@ -172,8 +167,7 @@ void reset_mirror(ksg_ctx* c) {
   c->pods.clear();
   c->seq = 0;
   c->patches.clear();
-  c->pending = false;
-  c->pend_srv = false;
+  c->pb.clear();
   c->upd_q.clear();
   c->q_added.clear();
   c->q_removed.clear();
@@ -216,38 +210,6 @@ int upload_pods(ksg_ctx* c, const ksg_pod* pods, uint32_t n, const uint32_t* ids
   return KSG_OK;
 }
 
-// the single-pod APIs: pod + ids staged contiguously, one copy into d_one;
-// one_pod / one_ids point into it until the next single-pod upload
-int upload_one(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, size_t n_ids) {
-  const size_t pb = (sizeof(ksg_pod) + 15) & ~(size_t)15, ib = std::max<size_t>(n_ids, 1) * sizeof(uint32_t);
-  // (extensions: the pod's ksg_pod_ext after the ids, all-zero for the plain entry points)
-  const size_t eo = (pb + ib + 15) & ~(size_t)15, eb = c->ext_on ? sizeof(ksg_pod_ext) : 0;
-  int rc = c->d_one.grow(c, eo + eb);
-  if (rc) return rc;
-  if ((rc = c->h_up.grow(c, eo + eb))) return rc;
-  memcpy(c->h_up, pod, sizeof(ksg_pod));
-  if (n_ids) memcpy(c->h_up + pb, ids, n_ids * sizeof(uint32_t));
-  if (eb) {
-    if (c->cur_ext) memcpy(c->h_up + eo, c->cur_ext, eb);
-    else memset(c->h_up + eo, 0, eb);
-  }
-  HIPCHK(c, hipMemcpyAsync(c->d_one, c->h_up, eb ? eo + eb : pb + (n_ids ? n_ids * sizeof(uint32_t) : 0),
-                           hipMemcpyHostToDevice, c->st));
-  c->one_pod = reinterpret_cast<const ksg_pod*>(c->d_one.p);
-  c->one_ids = reinterpret_cast<const uint32_t*>(c->d_one + pb);
-  c->d_one_ext = eb ? reinterpret_cast<ksg_pod_ext*>(c->d_one + eo) : nullptr;
-  return KSG_OK;
-}
-
-int ensure_map(ksg_ctx* c) {
-  if (c->h_map) return KSG_OK;
-  HIPCHK(c, hipHostMalloc((void**)&c->h_map, 64, hipHostMallocCoherent));
-  void* dp = nullptr;
-  HIPCHK(c, hipHostGetDevicePointer(&dp, c->h_map, 0));
-  c->d_map = static_cast<uint8_t*>(dp);
-  return KSG_OK;
-}
-
 size_t pod_ids_extent(const ksg_pod* p) {
   size_t e = 0;
   e = std::max<size_t>(e, (size_t)p->ports_off + p->n_ports);
@@ -256,16 +218,6 @@ size_t pod_ids_extent(const ksg_pod* p) {
   e = std::max<size_t>(e, (size_t)p->svcs_off + p->n_svcs);
   return e;
 }
-// ... and the extension record's taint lists (the single-pod _ext entry points)
-size_t call_ids_extent(const ksg_ctx* c, const ksg_pod* p) {
-  size_t e = pod_ids_extent(p);
-  if (c->cur_ext) {
-    e = std::max<size_t>(e, (size_t)c->cur_ext->hard_off + c->cur_ext->n_hard);
-    e = std::max<size_t>(e, (size_t)c->cur_ext->soft_off + c->cur_ext->n_soft);
-  }
-  return e;
-}
-
 // the shard records decide reads: all-gathered (exchange path) or this rank's own
 uint8_t* rec_buf(ksg_ctx* c) { return c->xchg ? c->cl.d_rec_recv.p : c->cl.d_rec_send.p; }
 
@@ -401,279 +353,6 @@ int wait_device(ksg_ctx* c) {
   return KSG_OK;
 }
 
-// ---- the resident drop-in server (ksg_serve.hip) ------------------------------
-// the grid server: plain configurations (no ServiceAntiAffinity, no extensions)
-// past srv_grid_min nodes, one scan workgroup per 256 nodes (<= 255)
-// nodes per thread of the grid server's scan workgroups
-uint32_t srv_npt(const ksg_ctx* c) { return c->cl.hi - c->cl.lo > c->srv_npt4_min ? 4u : 1u; }
-
-bool srv_grid(const ksg_ctx* c) {
-  const uint32_t n = c->cl.hi - c->cl.lo, per = KSG_GSRV_NT * srv_npt(c);
-  // (extensions: the filters and BalancedAllocation are per node; TaintToleration normalises over
-  // the filtered set: the scan workgroups exchange their maxima through device memory)
-  // (ServiceAntiAffinity: the domain counts likewise, up to KSG_GSRV_MAXD domains, without extensions)
-  return c->srv_grid_on && !(anti_on(c) && (c->ext_on || c->cl.dev.n_domains_total > KSG_GSRV_MAXD)) &&
-         !(c->ext_on && !c->srv_grid_ext) &&
-         n > c->srv_grid_min &&
-         (n + per - 1) / per <= KSG_GSRV_MAXW;
-}
-
-bool srv_eligible(const ksg_ctx* c) {
-  return c->srv_enabled && c->world == 1 && !c->xchg && (c->cl.R <= KSG_SRV_MAX_R || srv_grid(c)) && !c->cl.dev.wide &&
-         c->cl.N > 0;
-}
-
-int srv_alloc(ksg_ctx* c) {
-  if (!c->srv_box) {
-    HIPCHK(c, hipHostMalloc((void**)&c->srv_box, sizeof(KsgSrvBox), hipHostMallocCoherent | hipHostMallocMapped));
-    memset(c->srv_box, 0, sizeof(KsgSrvBox));
-    void* dp = nullptr;
-    HIPCHK(c, hipHostGetDevicePointer(&dp, c->srv_box, 0));
-    c->srv_dbox = static_cast<KsgSrvBox*>(dp);
-  }
-  return KSG_OK;
-}
-
-// (Re)launches the server on the stream, offering every request after the last
-// one answered. A COMMIT is posted without waiting for its answer, so the host's
-// srv_served may lag the server's: the response block names the last request the
-// server answered, and a server answers a request only once it will complete it
-// (the one-workgroup server applies a COMMIT's delta after answering it, before
-// it reads the next request or returns). Relaunching at srv_served alone would
-// offer an answered COMMIT again and apply its delta twice.
-int srv_launch(ksg_ctx* c) {
-  if (int rc = srv_alloc(c)) return rc;
-  const uint32_t r0 = __atomic_load_n(&c->srv_box->resp[0], __ATOMIC_ACQUIRE);
-  if ((int32_t)(r0 - c->srv_served) > 0) c->srv_served = r0;
-  const uint32_t start_seq = c->srv_served;
-  const size_t nf = ((size_t)(c->cl.hi - c->cl.lo) + 3 & ~(size_t)3) + 64;  // (the grid server stores 4 codes at a time)
-  if (c->srv_fail_cap < nf) {
-    if (c->srv_fail) (void)hipHostFree(c->srv_fail);
-    c->srv_fail = nullptr;
-    c->srv_fail_cap = 0;
-    HIPCHK(c, hipHostMalloc((void**)&c->srv_fail, nf, hipHostMallocCoherent | hipHostMallocMapped));
-    void* dp = nullptr;
-    HIPCHK(c, hipHostGetDevicePointer(&dp, c->srv_fail, 0));
-    c->srv_dfail = static_cast<uint8_t*>(dp);
-    c->srv_fail_cap = nf;
-  }
-  KsgSrvArgs a{c->srv_dbox, c->srv_dfail, start_seq, (uint64_t)c->srv_idle_us * 100,
-               (c->srv_stamps ? 1u : 0u) | (c->srv_debug ? 2u : 0u),
-               nullptr, 0, ++c->srv_epoch, 0};
-  if (srv_grid(c)) {
-    const uint32_t n = c->cl.hi - c->cl.lo;
-    const size_t need = sizeof(KsgSrvGrid);
-    if (c->srv_grid_cap < need) {
-      if (c->srv_grid) (void)hipFree(c->srv_grid);
-      c->srv_grid = nullptr;
-      c->srv_grid_cap = 0;
-      HIPCHK(c, hipMalloc((void**)&c->srv_grid, need));
-      HIPCHK(c, hipMemsetAsync(c->srv_grid, 0, need, c->st));
-      c->srv_grid_cap = need;
-    }
-    a.grid = c->srv_grid;
-    const uint32_t npt = srv_npt(c);
-    a.n_workers = (n + KSG_GSRV_NT * npt - 1) / (KSG_GSRV_NT * npt);
-    // past 64 scan workgroups their polls of the host block crowd the link: each sleeps ~0.2 us
-    // more between polls (measured: 50,000 nodes 73 -> 38 us per pod; no gain at 15,000)
-    a.grid_opts = c->srv_grid_opts >= 0 ? (uint32_t)c->srv_grid_opts : a.n_workers > 64 ? 0x10u : 0u;
-    HIPCHK(c, ksg_launch_serve_grid((int)npt, c->ext_on, c->cl.dev, a, c->st));
-  } else {
-    HIPCHK(c, ksg_launch_serve(c->cl.R, anti_on(c), c->ext_on, c->cl.dev, a, c->st));
-  }
-  c->srv_running = true;
-  ++c->srv_launches;
-  return KSG_OK;
-}
-
-// Waits until request `seq` is answered: its response, or (a grid server's
-// BEGIN, parts > 0) that many parts. A server that returned (idle) before it saw
-// the request is relaunched to serve it.
-int srv_wait(ksg_ctx* c, uint32_t seq, uint32_t parts) {
-  const uint32_t* rs = c->srv_box->resp;
-  auto done = [&]() {
-    if (!parts) return (int32_t)(__atomic_load_n(&rs[0], __ATOMIC_ACQUIRE) - seq) >= 0;  // (answered in order)
-    for (uint32_t q = 0; q < parts; ++q)
-      if (__atomic_load_n(&c->srv_box->part[q].seq, __ATOMIC_ACQUIRE) != seq ||
-          __atomic_load_n(&c->srv_box->part[q].stamp[3], __ATOMIC_ACQUIRE) != seq)  // (both ends of the store)
-        return false;
-    return true;
-  };
-  auto t0 = std::chrono::steady_clock::now();
-  uint32_t spins = 0, relaunches = 0;
-  while (!done()) {
-    if ((++spins & 255) != 0) continue;
-    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    if (us < 20.0) continue;
-    const hipError_t q = hipStreamQuery(c->st);
-    if (q == hipSuccess) {  // the server returned without serving `seq`
-      if (done()) break;
-      if (++relaunches > 3) return fail(c, KSG_ERR_HIP, "drop-in server exits without serving request %u", seq);
-      c->srv_running = false;
-      if (c->srv_trace) fprintf(stderr, "srv relaunch start %u (waiting %u)\n", c->srv_served, seq);
-      if (int rc = srv_launch(c)) return rc;  // (every request after the last answered one is offered again)
-      t0 = std::chrono::steady_clock::now();
-    } else if (q != hipErrorNotReady) {
-      c->srv_running = false;
-      std::string marks;
-      if (c->srv_debug)  // where each workgroup was (seq:stage), leader first
-        for (int i = 0; i < 12; ++i) {
-          const uint32_t m = __atomic_load_n(&c->srv_box->dbg[i], __ATOMIC_RELAXED);
-          marks += " " + std::to_string(m >> 8) + ":" + std::to_string(m & 255);
-        }
-      return fail(c, KSG_ERR_HIP, "drop-in server: %s (request %u%s)", hipGetErrorString(q), seq, marks.c_str());
-    } else if (us > 5e6) {
-      return fail(c, KSG_ERR_HIP, "drop-in server did not answer request %u in 5 s", seq);
-    }
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  if ((int32_t)(seq - c->srv_served) > 0) c->srv_served = seq;  // (and every request before it)
-  return KSG_OK;
-}
-
-// The control block is free once the server has read the last COMMIT (posted
-// without waiting for its answer): before the host writes a control request.
-int srv_settle(ksg_ctx* c) {
-  if (!c->srv_unacked) return KSG_OK;
-  const uint32_t u = c->srv_unacked;
-  c->srv_unacked = 0;
-  if ((int32_t)(c->srv_served - u) < 0)
-    if (int rc = srv_wait(c, u, 0)) return rc;
-  // resp[KSG_SRV_RESP_REJECTED]: the last request the server rejected, written before its
-  // response (later BEGIN answers overwrite resp[0..3], not this word). The host mirror
-  // already holds the commit's pod and the device does not: the context is diverged.
-  if (__atomic_load_n(&c->srv_box->resp[KSG_SRV_RESP_REJECTED], __ATOMIC_ACQUIRE) == u) {
-    c->diverged = true;
-    return fail(c, KSG_ERR_STATE, "drop-in server rejected commit request %u (ksg_set_cluster resyncs)", u);
-  }
-  return KSG_OK;
-}
-
-// Posts request ++srv_seq (header dwords hdr[0..KSG_SRV_HDR_DW); the payload
-// chunks were written by the caller): a BEGIN into `req`, a control request into
-// `creq` once the last COMMIT there was read. A BEGIN carries the last control
-// request before it (ARG).
-int srv_post(ksg_ctx* c, const uint32_t* hdr_in, uint32_t* seq_out) {
-  if (!c->srv_running) {
-    if (int rc = srv_launch(c)) return rc;
-  }
-  const bool ctl = hdr_in[KSG_SRVH_KIND] != KSG_SRV_BEGIN;
-  if (ctl) {
-    if (int rc = srv_settle(c)) return rc;
-  }
-  uint32_t hdr[KSG_SRV_HDR_DW];
-  memcpy(hdr, hdr_in, sizeof hdr);
-  if (!ctl) hdr[KSG_SRVH_ARG] = c->srv_last_ctl;
-  if (c->cl.dbg_corrupt) {
-    const uint32_t bit = hdr[KSG_SRVH_KIND] == KSG_SRV_COMMIT ? 1u : hdr[KSG_SRVH_KIND] == KSG_SRV_BEGIN ? 2u : 0u;
-    if (c->cl.dbg_corrupt & bit) {
-      hdr[KSG_SRVH_IDS_AT] = KSG_SRV_PAY_DW + 1;  // (past the payload: req_bad)
-      c->cl.dbg_corrupt &= ~bit;
-    }
-  }
-  const uint32_t seq = ++c->srv_seq;
-  if (ctl) c->srv_last_ctl = seq;
-  if (c->srv_trace)
-    fprintf(stderr, "srv post %u kind %u arg %u served %u\n", seq, hdr[KSG_SRVH_KIND], hdr[KSG_SRVH_ARG], c->srv_served);
-  uint32_t* req = ctl ? c->srv_box->creq : c->srv_box->req;
-  for (uint32_t i = 0; i < KSG_SRV_HDR_DW; ++i) req[4 * (i / KSG_SRV_CHUNK_DW) + i % KSG_SRV_CHUNK_DW] = hdr[i];
-  std::atomic_thread_fence(std::memory_order_release);  // data, then tags (x86: stores stay in order)
-  for (uint32_t q = 0; q < KSG_SRV_CHUNKS; ++q) __atomic_store_n(&req[4 * q + 3], seq, __ATOMIC_RELEASE);
-  *seq_out = seq;
-  return KSG_OK;
-}
-
-// Posts a request and waits for its response {seq, a, b, c}.
-int srv_call(ksg_ctx* c, const uint32_t* hdr, uint32_t* resp4) {
-  uint32_t seq = 0;
-  if (int rc = srv_post(c, hdr, &seq)) return rc;
-  if (int rc = srv_wait(c, seq, 0)) return rc;
-  const uint32_t* rs = c->srv_box->resp;
-  for (int i = 0; i < 4; ++i) resp4[i] = __atomic_load_n(&rs[i], __ATOMIC_RELAXED);
-  if (c->srv_stamps && hdr[KSG_SRVH_KIND] == KSG_SRV_BEGIN && __atomic_load_n(&rs[10], __ATOMIC_RELAXED) == seq) {
-    for (int i = 0; i < 6; ++i) c->srv_stage[i] += (int32_t)__atomic_load_n(&rs[4 + i], __ATOMIC_RELAXED);
-    ++c->srv_stamped;
-  }
-  return KSG_OK;
-}
-
-// A BEGIN on either server: {k | ~0u (no peer) | KSG_SRV_BADREQ, max} and the
-// tie words into srv_tw. The grid server's parts are merged here.
-int srv_begin(ksg_ctx* c, const uint32_t* hdr, uint32_t* resp4) {
-  const uint32_t n = c->cl.hi - c->cl.lo, nwd = (n + 63) / 64;
-  if (!srv_grid(c)) {
-    if (int rc = srv_call(c, hdr, resp4)) return rc;
-    if (resp4[1] != KSG_SRV_BADREQ && resp4[1] != ~0u && resp4[1] > 0)
-      c->srv_tw.assign(c->srv_box->ties, c->srv_box->ties + nwd);
-    return KSG_OK;
-  }
-  const uint32_t npt = srv_npt(c), G = (n + KSG_GSRV_NT * npt - 1) / (KSG_GSRV_NT * npt), NWG = 4 * npt;
-  uint32_t seq = 0;
-  if (int rc = srv_post(c, hdr, &seq)) return rc;
-  if (int rc = srv_wait(c, seq, G)) return rc;
-  const KsgSrvPart* pt = c->srv_box->part;
-  int32_t M = KSG_S32_NONE;
-  uint32_t err = 0;
-  for (uint32_t q = 0; q < G; ++q) {
-    M = std::max(M, pt[q].max);
-    err |= pt[q].err;
-  }
-  uint32_t k = 0;
-  c->srv_tw.assign((size_t)G * NWG, 0);
-  if (M != KSG_S32_NONE)
-    for (uint32_t q = 0; q < G; ++q)
-      if (pt[q].max == M) {
-        k += pt[q].cnt;
-        const uint64_t* tw = npt == 1 ? pt[q].tie : c->srv_box->part_tie + (size_t)q * KSG_GSRV_TIEW;
-        for (uint32_t r = 0; r < NWG; ++r) c->srv_tw[(size_t)q * NWG + r] = tw[r];
-      }
-  c->srv_tw.resize(nwd);
-  if (c->srv_stamps) {  // worker 0: masks + loads, eval + publish (100-MHz ticks)
-    c->srv_stage[0] += (int32_t)(pt[0].stamp[1] - pt[0].stamp[0]);
-    c->srv_stage[1] += (int32_t)(pt[0].stamp[2] - pt[0].stamp[1]);  // (stamp[3]: the sequence number)
-    ++c->srv_stamped;
-  }
-  resp4[0] = seq;
-  resp4[1] = (err & 2) ? KSG_SRV_BADREQ : err ? ~0u : k;
-  if (c->srv_trace) fprintf(stderr, "srv begin %u max %d k %u err %u\n", seq, M, k, err);
-  const int64_t m64 = M;
-  resp4[2] = (uint32_t)(uint64_t)m64;
-  resp4[3] = (uint32_t)((uint64_t)m64 >> 32);
-  return KSG_OK;
-}
-
-// the t-th set bit (ascending) of the tie words -> node offset, -1 if none
-int64_t srv_pick(const std::vector<uint64_t>& tw, uint64_t t) {
-  uint64_t acc = 0;
-  for (size_t i = 0; i < tw.size(); ++i) {
-    const uint64_t pc = (uint64_t)__builtin_popcountll(tw[i]);
-    if (t < acc + pc) {
-      uint64_t w = tw[i];
-      for (uint64_t j = acc; j < t; ++j) w &= w - 1;  // drop the lower set bits
-      return (int64_t)(i * 64 + (uint64_t)__builtin_ctzll(w));
-    }
-    acc += pc;
-  }
-  return -1;
-}
-
-// Ends the resident server so other work can use the stream.
-int srv_stop(ksg_ctx* c) {
-  if (!c->srv_running) return KSG_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (int rc = srv_settle(c)) return rc;  // (the last commit is applied first)
-  if (hipStreamQuery(c->st) != hipSuccess) {
-    uint32_t hdr[KSG_SRV_HDR_DW] = {KSG_SRV_EXIT};
-    uint32_t r[4];
-    if (int rc = srv_call(c, hdr, r)) return rc;
-  }
-  c->srv_running = false;
-  // (a pending begin served by the server stays pending: its commit picks the node from
-  // srv_tw on the host and posts the COMMIT to a relaunched server)
-  HIPCHK(c, hipStreamSynchronize(c->st));
-  return KSG_OK;
-}
-
 // int64 combined scores (the exact kernels; the window path and the resident servers are
 // int32): once a |score| could reach KSG_SCORE_BOUND by the weights, or a LeastRequested
 // term can leave the [0, 10] that bound assumes
@@ -701,123 +380,6 @@ int note_requests(ksg_ctx* c, const ksg_pod* pods, uint32_t n) {
   if (!c->cl.dev.wide) {
     if (int rc = srv_stop(c)) return rc;
     set_wide(c);
-  }
-  return KSG_OK;
-}
-
-int srv_flush_patches(ksg_ctx* c) {
-  if (int rc = srv_alloc(c)) return rc;
-  size_t at = 0;
-  while (at < c->patches.size()) {
-    const uint32_t n = (uint32_t)std::min<size_t>(c->patches.size() - at, KSG_SRV_PATCHES);
-    memcpy(c->srv_box->patch, c->patches.data() + at, (size_t)n * sizeof(KsgPatch));
-    uint32_t hdr[KSG_SRV_HDR_DW] = {KSG_SRV_PATCH};
-    hdr[KSG_SRVH_NPATCH] = n;
-    uint32_t r[4];
-    if (int rc = srv_call(c, hdr, r)) return rc;
-    at += n;
-  }
-  c->patches.clear();
-  return KSG_OK;
-}
-
-// The pod, its ids [0, n_ids) and (extensions) its record as the request
-// payload; false if it does not fit the block + ext area.
-bool srv_put_pod(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, size_t n_ids, const ksg_pod_ext* ext,
-                 uint32_t* hdr, bool ctl = false) {
-  const uint32_t pod_dw = (uint32_t)(sizeof(ksg_pod) / 4), ext_dw = (uint32_t)(sizeof(ksg_pod_ext) / 4);
-  const uint32_t ids_at = pod_dw;
-  const uint32_t ext_at = (ids_at + (uint32_t)n_ids + 1) & ~1u;  // 8-byte aligned
-  const uint64_t paydw = ext ? (uint64_t)ext_at + ext_dw : (uint64_t)ids_at + n_ids;
-  if (paydw > KSG_SRV_PAY_DW) return false;
-  uint32_t* req = ctl ? c->srv_box->creq : c->srv_box->req;
-  uint32_t* xa = ctl ? c->srv_box->cext : c->srv_box->ext;
-  auto put = [&](uint32_t i, uint32_t v) {  // payload dword i
-    if (i < KSG_SRV_INLINE_DW) {
-      const uint32_t j = KSG_SRV_HDR_DW + i;
-      req[4 * (j / KSG_SRV_CHUNK_DW) + j % KSG_SRV_CHUNK_DW] = v;
-    } else {
-      xa[i - KSG_SRV_INLINE_DW] = v;
-    }
-  };
-  const uint32_t* pw = reinterpret_cast<const uint32_t*>(pod);
-  for (uint32_t i = 0; i < pod_dw; ++i) put(i, pw[i]);
-  for (uint32_t i = 0; i < n_ids; ++i) put(ids_at + i, ids[i]);
-  if (ext) {
-    const uint32_t* ew = reinterpret_cast<const uint32_t*>(ext);
-    for (uint32_t i = 0; i < ext_dw; ++i) put(ext_at + i, ew[i]);
-  }
-  hdr[KSG_SRVH_PAYDW] = (uint32_t)paydw;
-  hdr[KSG_SRVH_IDS_AT] = ids_at;
-  hdr[KSG_SRVH_EXT_AT] = ext_at;
-  if (ext) hdr[KSG_SRVH_FLAGS] |= KSG_SRVF_EXT;
-  return true;
-}
-
-// ---- the read-only batch queries' frame (ksg_host.h) --------------------------
-int query_enter(ksg_ctx* c, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids, uint32_t n_ids, double* last_ms) {
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
-  if (ext && !c->ext_on) return fail(c, KSG_ERR_STATE, "extensions are off");
-  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
-  if (int rc0 = flush_deferred(c)) return rc0;  // (the mirror now holds the last batch)
-  if (int rs = cluster_ok(c)) return rs;
-  HIPCHK(c, hipSetDevice(c->device));
-  *last_ms = 0.0;
-  if (n == 0) return kQueryDone;
-  if (c->cl.N == 0) return KSG_NONODES;
-  if (n_ids && !ids) return fail(c, KSG_ERR_ARG, "ids missing");
-  return KSG_OK;
-}
-
-int query_validate(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
-                   uint32_t n_ids, const std::function<int(uint32_t)>& also) {
-  int rc;
-  for (uint32_t i = 0; i < n; ++i) {
-    if ((rc = check_pod(c, pods + i, ids, n_ids))) return rc;
-    if (ext && ((rc = check_ext_range(c, ext + i, n_ids)) || (rc = check_taint_ids(c, ext + i, ids)))) return rc;
-    if (also && (rc = also(i))) return rc;
-  }
-  return KSG_OK;
-}
-
-int query_upload(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
-                 uint32_t n_ids, bool zero_records, const ksg_pod_ext** dext) {
-  int rc;
-  *dext = nullptr;
-  if ((rc = flush_patches(c))) return rc;
-  if ((rc = upload_pods(c, pods, n, ids, n_ids))) return rc;
-  if (!(ext || (zero_records && c->ext_on))) return KSG_OK;
-  if ((rc = c->d_pext.grow(c, n))) return rc;
-  if (ext) HIPCHK(c, hipMemcpyAsync(c->d_pext, ext, (size_t)n * sizeof(ksg_pod_ext), hipMemcpyHostToDevice, c->st));
-  else HIPCHK(c, hipMemsetAsync(c->d_pext, 0, (size_t)n * sizeof(ksg_pod_ext), c->st));
-  *dext = c->d_pext;
-  return KSG_OK;
-}
-
-uint32_t query_per(size_t budget, size_t bytes_per_pod, uint32_t chunk, uint32_t n) {
-  uint32_t per = 1u << 20;  // (the grid's y extent stays far below 65,535)
-  if (bytes_per_pod) per = (uint32_t)std::min<size_t>(per, std::max<size_t>(budget / bytes_per_pod, 1));
-  if (per > chunk) per -= per % chunk;
-  return std::min(per, n);
-}
-
-int query_chunks(ksg_ctx* c, uint32_t n, uint32_t per, double* last_ms, const std::function<int(uint32_t, uint32_t)>& launch,
-                 const std::function<int(uint32_t, uint32_t, bool)>& copies) {
-  int rc;
-  if (!c->ev_x0) {
-    HIPCHK(c, hipEventCreate(&c->ev_x0));
-    HIPCHK(c, hipEventCreate(&c->ev_x1));
-  }
-  for (uint32_t a = 0; a < n; a += per) {
-    const uint32_t m = std::min(per, n - a);
-    HIPCHK(c, hipEventRecord(c->ev_x0, c->st));
-    if ((rc = launch(a, m))) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_x1, c->st));
-    if ((rc = copies(a, m, a + per >= n))) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->st));  // (the staging buffers are reused by the next chunk)
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev_x0, c->ev_x1));
-    *last_ms += ms;
   }
   return KSG_OK;
 }
@@ -896,7 +458,7 @@ static int create_impl(const ksg_config* cfg, int device, int rank, int world, c
   c->device = device;
   c->rank = rank;
   c->world = world;
-  auto bail = [&](int rc) {
+  auto bail = [&](int rc) {  // (the half-built context frees what it holds: the owners of ksg_host.h)
     if (rc != KSG_OK) {
       fprintf(stderr, "ksg_create: %s\n", c->err.c_str());
       delete c;
@@ -905,22 +467,12 @@ static int create_impl(const ksg_config* cfg, int device, int rank, int world, c
   };
   hipError_t e = hipSetDevice(device);
   if (e != hipSuccess) return bail(fail(c, KSG_ERR_HIP, "hipSetDevice(%d): %s", device, hipGetErrorString(e)));
-  if ((e = hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipEventCreateWithFlags(&c->ev0, kTimingEvent)) != hipSuccess ||
-      (e = hipEventCreateWithFlags(&c->ev1, kTimingEvent)) != hipSuccess ||
-      (e = hipEventCreateWithFlags(&c->ev_wait, hipEventDisableTiming)) != hipSuccess)
+  if ((e = hipStreamCreateWithFlags(&c->st.s, hipStreamNonBlocking)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&c->ev0.e, kTimingEvent)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&c->ev1.e, kTimingEvent)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&c->ev_wait.e, hipEventDisableTiming)) != hipSuccess)
     return bail(fail(c, KSG_ERR_HIP, "stream/event: %s", hipGetErrorString(e)));
   c->spin_wait = env_flag("KSG_SPIN_WAIT", true);
-  c->srv_enabled = env_flag("KSG_SERVE", true);
-  c->srv_stamps = env_flag("KSG_SERVE_STAMPS", false);
-  c->srv_debug = env_flag("KSG_SERVE_DEBUG", false);
-  c->srv_trace = env_flag("KSG_SERVE_TRACE", false);
-  if (const char* go = getenv("KSG_SERVE_GRID_OPTS")) c->srv_grid_opts = (int64_t)strtoul(go, nullptr, 0);
-  c->srv_idle_us = (uint64_t)env_int("KSG_SERVE_IDLE_US", (int64_t)c->srv_idle_us, 1, INT64_MAX);
-  c->srv_grid_on = env_flag("KSG_SERVE_GRID", true);
-  c->srv_grid_min = (uint32_t)env_int("KSG_SERVE_GRID_MIN", c->srv_grid_min, 0, INT32_MAX);
-  c->srv_npt4_min = (uint32_t)env_int("KSG_SERVE_GRID_NPT4_MIN", c->srv_npt4_min, 0, INT32_MAX);
-  c->srv_grid_ext = env_flag("KSG_SERVE_GRID_EXT", true);
   if (const char* rm = getenv("KSG_ROUND_MARGIN")) c->round_margin = std::min(std::max(atof(rm), 0.5), 4.0);
   // ksg_headroom_batch: the staging budget of the per-node counts (a test knob: a chunk
   // boundary at a small shape) and the quotient's variant (measurements)
@@ -939,17 +491,16 @@ static int create_impl(const ksg_config* cfg, int device, int rank, int world, c
     if (nccl_id) {  // else: the caller installs a host transport with ksg_set_allgather
       ncclUniqueId id;
       memcpy(&id, nccl_id, sizeof id);
-      ncclResult_t r = ncclCommInitRank(&c->comm, world, id, rank);
+      ncclResult_t r = ncclCommInitRank(&c->comm.c, world, id, rank);
       if (r != ncclSuccess) return bail(fail(c, KSG_ERR_RCCL, "ncclCommInitRank: %s", ncclGetErrorString(r)));
     }
   }
   int rc;
   c->window = (uint32_t)env_int("KSG_WINDOW", c->window, INT32_MIN, INT32_MAX);
   c->ev_stride = (uint32_t)env_int("KSG_KERNEL_EVENTS", c->ev_stride, 0, INT32_MAX);
-  if ((rc = dalloc(c, c->d_rng, 1)) || (rc = dalloc(c, c->d_summary, 4)) || (rc = dalloc(c, c->d_run, 1)))
+  if ((rc = dalloc(c, c->d_rng, 1)) || (rc = dalloc(c, c->d_summary, 4)) || (rc = dalloc(c, c->d_run, 1)) ||
+      (rc = c->h_run.alloc(c, 1)))
     return bail(rc);
-  if ((e = hipHostMalloc((void**)&c->h_run, sizeof(KsgWinRun), hipHostMallocDefault)) != hipSuccess)
-    return bail(fail(c, KSG_ERR_HIP, "hipHostMalloc: %s", hipGetErrorString(e)));
   c->win_fused = env_flag("KSG_FUSED", true);
   {
     int cus = 0;
@@ -959,9 +510,8 @@ static int create_impl(const ksg_config* cfg, int device, int rank, int world, c
     if (c->fused_grid == 0) c->win_fused = false;
     c->fused_max_words = (uint32_t)env_int("KSG_FUSED_MAX_WORDS", c->fused_max_words, 0, INT32_MAX);
   }
-  if ((e = hipMalloc((void**)&c->d_fctl, kFctlBytes)) != hipSuccess ||
-      (e = hipHostMalloc((void**)&c->h_fctl, kFctlBytes, hipHostMallocDefault)) != hipSuccess)
-    return bail(fail(c, KSG_ERR_HIP, "fused window control: %s", hipGetErrorString(e)));
+  if ((rc = c->d_fctl.grow(c, kFctlBytes)) || (rc = c->h_fctl.alloc(c, kFctlBytes)))
+    return bail(fail(c, rc, "fused window control: %s", std::string(c->err).c_str()));
   memset(c->h_fctl, 0, kFctlBytes);
   *out = c;
   return KSG_OK;
@@ -996,37 +546,11 @@ int ksg_destroy(ksg_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)srv_stop(c);
   }
-  if (c->srv_stamped && srv_grid(c)) {
-    const double n = (double)c->srv_stamped;
-    fprintf(stderr, "ksg grid serve stamps (10-ns ticks per begin, %llu begins, scan workgroup 0): request seen -> "
-            "masks + loads done %.1f, -> eval + part stored %.1f\n",
-            (unsigned long long)c->srv_stamped, c->srv_stage[0] / n, c->srv_stage[1] / n);
-  } else if (c->srv_stamped) {
-    const double n = (double)c->srv_stamped;
-    fprintf(stderr, "ksg serve stamps (s_memtime cycles per begin, %llu begins): to-LDS %.0f check %.0f resolve %.0f "
-            "scan %.0f reduce %.0f fail-codes %.0f\n", (unsigned long long)c->srv_stamped, c->srv_stage[0] / n,
-            c->srv_stage[1] / n, c->srv_stage[2] / n, c->srv_stage[3] / n, c->srv_stage[4] / n, c->srv_stage[5] / n);
-  }
+  srv_print_stamps(c);
   (void)hipSetDevice(c->device);
   if (c->st) (void)hipStreamSynchronize(c->st);
-  if (c->comm) ncclCommDestroy(c->comm);
-  if (c->h_run) (void)hipHostFree(c->h_run);
-  if (c->h_fctl) (void)hipHostFree(c->h_fctl);
-  if (c->d_fctl) (void)hipFree(c->d_fctl);
-  if (c->h_map) (void)hipHostFree(c->h_map);
-  if (c->srv_box) (void)hipHostFree(c->srv_box);
-  if (c->srv_grid) (void)hipFree(c->srv_grid);
-  if (c->srv_fail) (void)hipHostFree(c->srv_fail);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  if (c->ev_wait) (void)hipEventDestroy(c->ev_wait);
-  if (c->ev_x0) (void)hipEventDestroy(c->ev_x0);
-  if (c->ev_x1) (void)hipEventDestroy(c->ev_x1);
-  for (auto& e : c->wev)
-    if (e) (void)hipEventDestroy(e);
-  if (c->st) (void)hipStreamDestroy(c->st);
-  // (the node list's parts, c->cl, and the scratch buffers free themselves: the device is set and
-  // the stream was synchronised above)
+  // (the members free and destroy themselves, the stream last: the device is set and the
+  // stream's work is done)
   delete c;
   return KSG_OK;
 }
@@ -1105,7 +629,7 @@ int remove_pod_impl(ksg_ctx* c, uint64_t uid) {
 }
 
 // apply the updates queued while a schedule_begin was pending (c->mu held)
-static int apply_queued(ksg_ctx* c) {
+int apply_queued(ksg_ctx* c) {
   std::vector<ksg_ctx::Queued> q;
   q.swap(c->upd_q);
   c->q_added.clear();
@@ -1122,13 +646,13 @@ int ksg_add_pod(ksg_ctx* c, uint32_t host_id, const ksg_pod* pod, const uint32_t
   KSG_LOCK(c);
   if (c->ext_on && !c->cur_ext) c->ext_scalar.erase(pod->uid);  // (plain entry point: no extension requests)
   HIPCHK(c, hipSetDevice(c->device));  // reflector threads: patches flush on this context's device
-  if (!c->pending) return add_pod_impl(c, host_id, pod, ids);
+  if (!c->pb.on) return add_pod_impl(c, host_id, pod, ids);
   if (int rs = cluster_ok(c)) return rs;
   const size_t ext = pod_ids_extent(pod);
   int rc = check_pod(c, pod, ids, ext);
   if (rc) return rc;
   const bool live = c->pods.count(pod->uid) && !c->q_removed.count(pod->uid);
-  if (live || c->q_added.count(pod->uid) || pod->uid == c->pend.uid)
+  if (live || c->q_added.count(pod->uid) || pod->uid == c->pb.pod.uid)
     return fail(c, KSG_ERR_ARG, "duplicate pod uid %llu", (unsigned long long)pod->uid);
   c->upd_q.push_back({true, host_id, *pod, std::vector<uint32_t>(ids, ids + ext), pod->uid});
   c->q_added.insert(pod->uid);
@@ -1140,194 +664,12 @@ int ksg_remove_pod(ksg_ctx* c, uint64_t uid) {
   if (!c) return KSG_ERR_ARG;
   KSG_LOCK(c);
   HIPCHK(c, hipSetDevice(c->device));
-  if (!c->pending) return remove_pod_impl(c, uid);
+  if (!c->pb.on) return remove_pod_impl(c, uid);
   const bool live = (c->pods.count(uid) && !c->q_removed.count(uid)) || c->q_added.count(uid);
   if (!live) return fail(c, KSG_ERR_ARG, "unknown pod uid %llu", (unsigned long long)uid);
   c->upd_q.push_back({false, 0, ksg_pod{}, {}, uid});
   c->q_added.erase(uid);
   c->q_removed.insert(uid);
-  return KSG_OK;
-}
-
-int ksg_schedule_begin(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, int64_t* max_score,
-                       uint32_t* tie_count, uint8_t* fail_codes) {
-  if (!c || !pod) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (int rc0 = flush_deferred(c)) return rc0;
-  if (int rs = cluster_ok(c)) return rs;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->pending) {  // the previous begin was abandoned: its queued updates apply now
-    c->pending = false;
-    c->pend_srv = false;
-    if (int rq = apply_queued(c)) return rq;
-  }
-  if (c->cl.N == 0) return KSG_NONODES;
-  if (c->ext_on && !c->cur_ext) c->ext_scalar.erase(pod->uid);  // (plain entry point: no extension requests)
-  const size_t ext = call_ids_extent(c, pod);
-  int rc = check_pod(c, pod, ids, ext);
-  if (rc) return rc;
-  if ((rc = note_requests(c, pod, 1))) return rc;
-  if (srv_eligible(c)) {  // the resident server: one request, no launch / copy / stream sync
-    uint32_t hdr[KSG_SRV_HDR_DW] = {KSG_SRV_BEGIN};
-    if ((rc = srv_alloc(c))) return rc;
-    // (an all-zero record for the plain entry point of an extensions context)
-    static const ksg_pod_ext zero_ext{};
-    const ksg_pod_ext* xr = c->ext_on ? (c->cur_ext ? c->cur_ext : &zero_ext) : nullptr;
-    // ServiceAffinity (predicates.go:257-324): the labels the pod's nodeSelector does not give come
-    // from its service's first peer's node; resolved here from the host mirror (svc_peer, kept equal
-    // to the device's) so the scan workgroups skip that dependent chain (pod_resolve then finds
-    // every requirement given; an unlabelled peer leaves -1, which it resolves to the same -1)
-    ksg_pod rp;
-    const ksg_pod* sp = pod;
-    if (!c->cl.h_aff_pair.empty() && pod->service >= 0 && (uint32_t)pod->service < c->cl.S) {
-      const int32_t peer = c->mir.svc_peer[pod->service];
-      bool given = true;
-      for (uint32_t j = 0; j < c->cfg.n_aff_labels && j < KSG_MAX_AFF; ++j) given = given && pod->aff_pair[j] != -1;
-      if (!given && peer >= 0 && (uint32_t)peer < c->cl.N) {
-        rp = *pod;
-        for (uint32_t j = 0; j < c->cfg.n_aff_labels && j < KSG_MAX_AFF; ++j)
-          if (rp.aff_pair[j] == -1) rp.aff_pair[j] = c->cl.h_aff_pair[(size_t)j * c->cl.N + (uint32_t)peer];
-        sp = &rp;
-      }
-    }
-    if (srv_put_pod(c, sp, ids, ext, xr, hdr)) {
-      if ((rc = flush_patches(c)) || (!c->srv_running && (rc = srv_flush_patches(c)))) return rc;
-      if (fail_codes) hdr[KSG_SRVH_FLAGS] |= KSG_SRVF_WANT_FAIL;
-      uint32_t r[4];
-      if ((rc = srv_begin(c, hdr, r))) return rc;
-      // (the last COMMIT was served before this BEGIN: a rejected one diverged the context)
-      if ((rc = srv_settle(c))) return rc;
-      if (r[1] == KSG_SRV_BADREQ) return fail(c, KSG_ERR_STATE, "drop-in server rejected begin request");
-      if (r[1] == ~0u) return fail(c, KSG_ERR_NOPEER, "service affinity peer is not on a known node");
-      if (fail_codes) memcpy(fail_codes, c->srv_fail, (size_t)(c->cl.hi - c->cl.lo));
-      const int64_t m = (int64_t)((uint64_t)r[2] | ((uint64_t)r[3] << 32));
-      if (max_score) *max_score = r[1] > 0 ? m : 0;
-      if (tie_count) *tie_count = r[1];
-      if (r[1] == 0) return KSG_NOFIT;
-      c->pending = true;
-      c->pending_k = r[1];
-      c->pend = *pod;
-      c->pend_ids.assign(ids, ids + ext);
-      c->pend_srv = true;
-      memcpy(c->srv_bhdr, hdr, sizeof hdr);
-      c->srv_pext_on = xr != nullptr;
-      if (xr) c->srv_pext = *xr;
-      return KSG_OK;
-    }
-  }
-  if ((rc = srv_stop(c))) return rc;
-  if ((rc = flush_patches(c))) return rc;
-  if ((rc = ensure_map(c)) || (rc = upload_one(c, pod, ids, ext))) return rc;
-  if ((rc = scan_exchange(c, c->one_pod, c->one_ids, KSG_MODE_BEGIN, fail_codes ? c->cl.d_fail : nullptr, nullptr,
-                          c->ext_on ? c->d_one_ext : nullptr)))
-    return rc;
-  HIPCHK(c, ksg_launch_decide(c->cl.dev, c->one_pod, c->one_ids, rec_buf(c), c->cl.rec_bytes, c->world,
-                              c->cl.d_shard_wlo, 0, 0, c->d_rng, nullptr, 0, reinterpret_cast<int64_t*>(c->d_map),
-                              c->st));
-  int64_t summ[3];
-  const size_t nf = fail_codes ? (size_t)(c->cl.hi - c->cl.lo) : 0;
-  if (nf) {
-    if ((rc = c->h_dn.grow(c, nf))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_dn, c->cl.d_fail, nf, hipMemcpyDeviceToHost, c->st));
-  }
-  HIPCHK(c, hipStreamSynchronize(c->st));
-  memcpy(summ, c->h_map, sizeof summ);
-  if (nf) memcpy(fail_codes, c->h_dn, nf);
-  if (summ[2]) return fail(c, KSG_ERR_NOPEER, "service affinity peer is not on a known node");
-  if (max_score) *max_score = summ[1] > 0 ? summ[0] : 0;
-  if (tie_count) *tie_count = (uint32_t)summ[1];
-  if (summ[1] == 0) return KSG_NOFIT;
-  c->pending = true;
-  c->pending_k = (uint64_t)summ[1];
-  c->pend = *pod;
-  c->pend_ids.assign(ids, ids + ext);
-  return KSG_OK;
-}
-
-// the device half of a commit: decide the tie_index-th tie and apply AssumePod's delta
-static int commit_on_device(ksg_ctx* c, uint32_t tie_index, int32_t* node) {
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->pend_srv) {  // served by the resident server
-    c->pend_srv = false;
-    // the tie_index-th tie from the top (generic_scheduler.go:88-95) from the begin's tie words
-    const int64_t off = srv_pick(c->srv_tw, c->pending_k - 1 - tie_index);
-    if (off < 0 || off >= (int64_t)(c->cl.hi - c->cl.lo)) return fail(c, KSG_ERR_STATE, "commit selected no node");
-    *node = (int32_t)(c->cl.lo + (uint32_t)off);
-    // AssumePod's delta: one control request carrying the pod, not waited for (the next
-    // BEGIN's scan waits on the device until it is applied)
-    uint32_t hdr[KSG_SRV_HDR_DW] = {KSG_SRV_COMMIT};
-    if (int rc = srv_settle(c)) return rc;  // (the control block is free)
-    if (!srv_put_pod(c, &c->pend, c->pend_ids.data(), c->pend_ids.size(), c->srv_pext_on ? &c->srv_pext : nullptr,
-                     hdr, true))
-      return fail(c, KSG_ERR_STATE, "pending pod does not fit the request block");
-    hdr[KSG_SRVH_ARG] = (uint32_t)*node;
-    if (c->srv_trace) fprintf(stderr, "srv commit node %d\n", *node);
-    uint32_t seq = 0;
-    if (int rc = srv_post(c, hdr, &seq)) return rc;
-    c->srv_unacked = seq;
-    return KSG_OK;
-  }
-  int rc = ensure_map(c);
-  if (rc) return rc;
-  if ((rc = srv_stop(c))) return rc;
-  // the pending pod is still in d_one (begin's upload; nothing re-uploads before the commit)
-  HIPCHK(c, ksg_launch_decide(c->cl.dev, c->one_pod, c->one_ids, rec_buf(c), c->cl.rec_bytes, c->world,
-                              c->cl.d_shard_wlo, 2, tie_index, c->d_rng, reinterpret_cast<int32_t*>(c->d_map + 32), 0,
-                              c->d_summary, c->st, c->ext_on ? c->d_one_ext : nullptr));
-  HIPCHK(c, hipStreamSynchronize(c->st));
-  memcpy(node, c->h_map + 32, 4);
-  if (*node < 0) return fail(c, KSG_ERR_STATE, "commit selected no node (%d)", *node);
-  return KSG_OK;
-}
-
-int ksg_schedule_commit(ksg_ctx* c, uint32_t tie_index, int32_t* out_node) {
-  if (!c) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (!c->pending) return fail(c, KSG_ERR_STATE, "no schedule_begin pending");
-  if (tie_index >= c->pending_k) return fail(c, KSG_ERR_ARG, "tie_index %u >= tie_count %llu", tie_index,
-                                             (unsigned long long)c->pending_k);
-  int32_t node = -1;
-  int rc = commit_on_device(c, tie_index, &node);
-  c->pending = false;
-  if (rc == KSG_OK) rc = mirror_add(c, (uint32_t)node, &c->pend, c->pend_ids.data(), false);
-  c->pend.uid = ~0ULL;
-  // the updates queued while the begin was pending apply now, whatever the outcome
-  const int rq = apply_queued(c);
-  if (rc) return rc;
-  if (rq) return rq;
-  if (out_node) *out_node = node;
-  return KSG_OK;
-}
-
-int ksg_evaluate(ksg_ctx* c, const ksg_pod* pod, const uint32_t* ids, uint8_t* fail_out, int64_t* score_out) {
-  if (!c || !pod) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (c->pending) return fail(c, KSG_ERR_STATE, "schedule_begin pending");
-  if (int rs_ = srv_stop(c)) return rs_;  // (the resident server leaves the stream)
-  if (int rc0 = flush_deferred(c)) return rc0;
-  if (int rs = cluster_ok(c)) return rs;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->cl.N == 0) return KSG_NONODES;
-  const size_t ext = call_ids_extent(c, pod);
-  int rc = check_pod(c, pod, ids, ext);
-  if (rc) return rc;
-  if ((rc = note_requests(c, pod, 1))) return rc;
-  if ((rc = flush_patches(c))) return rc;
-  if ((rc = upload_one(c, pod, ids, ext))) return rc;
-  // errors surface through the BEGIN record, so run BEGIN first for the flag
-  if ((rc = scan_exchange(c, c->one_pod, c->one_ids, KSG_MODE_BEGIN, nullptr, nullptr, c->ext_on ? c->d_one_ext : nullptr)))
-    return rc;
-  HIPCHK(c, ksg_launch_decide(c->cl.dev, c->one_pod, c->one_ids, rec_buf(c), c->cl.rec_bytes, c->world,
-                              c->cl.d_shard_wlo, 0, 0, c->d_rng, nullptr, 0, c->d_summary, c->st));
-  if ((rc = scan_exchange(c, c->one_pod, c->one_ids, KSG_MODE_EVAL, c->cl.d_fail, c->cl.d_score, c->ext_on ? c->d_one_ext : nullptr)))
-    return rc;
-  int64_t summ[3];
-  HIPCHK(c, hipMemcpyAsync(summ, c->d_summary, sizeof summ, hipMemcpyDeviceToHost, c->st));
-  const size_t ns = c->cl.hi - c->cl.lo;
-  if (fail_out && ns) HIPCHK(c, hipMemcpyAsync(fail_out, c->cl.d_fail, ns, hipMemcpyDeviceToHost, c->st));
-  if (score_out && ns) HIPCHK(c, hipMemcpyAsync(score_out, c->cl.d_score, ns * 8, hipMemcpyDeviceToHost, c->st));
-  HIPCHK(c, hipStreamSynchronize(c->st));
-  if (summ[2]) return fail(c, KSG_ERR_NOPEER, "service affinity peer is not on a known node");
   return KSG_OK;
 }
 
@@ -1337,16 +679,6 @@ int ksg_set_allgather(ksg_ctx* c, ksg_allgather_fn fn, void* user) {
   if (c->comm) return fail(c, KSG_ERR_STATE, "context already exchanges over RCCL");
   c->xfn = fn;
   c->xuser = user;
-  return KSG_OK;
-}
-
-int ksg_serve_stats(ksg_ctx* c, uint64_t* out4) {
-  if (!c || !out4) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  out4[0] = c->srv_launches;
-  out4[1] = c->srv_seq;
-  out4[2] = c->srv_running ? 1 : 0;
-  out4[3] = srv_eligible(c) ? (srv_grid(c) ? 2 : 1) : 0;
   return KSG_OK;
 }
 
@@ -1536,209 +868,6 @@ int ksg_add_pod_ext(ksg_ctx* c, uint32_t host_id, const ksg_pod* pod, const ksg_
   const int rc = ksg_add_pod(c, host_id, pod, ids);
   c->cur_ext = nullptr;
   return rc;
-}
-
-int ksg_schedule_begin_ext(ksg_ctx* c, const ksg_pod* pod, const ksg_pod_ext* ext, const uint32_t* ids,
-                           int64_t* max_score, uint32_t* tie_count, uint8_t* fail_codes) {
-  if (!c || !pod) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (ext && !c->ext_on) return fail(c, KSG_ERR_STATE, "extensions are off");
-  c->cur_ext = ext;
-  int rc = KSG_OK;
-  if (ext) {
-    const size_t n_ids = call_ids_extent(c, pod);
-    if (!(rc = check_ext_range(c, ext, n_ids)) && !(rc = check_taint_ids(c, ext, ids))) rc = note_ext(c, pod, ext, n_ids);
-  }
-  if (!rc) rc = ksg_schedule_begin(c, pod, ids, max_score, tie_count, fail_codes);
-  c->cur_ext = nullptr;
-  return rc;
-}
-
-int ksg_evaluate_ext(ksg_ctx* c, const ksg_pod* pod, const ksg_pod_ext* ext, const uint32_t* ids, uint8_t* fail_out,
-                     int64_t* score_out) {
-  if (!c || !pod) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (ext && !c->ext_on) return fail(c, KSG_ERR_STATE, "extensions are off");
-  c->cur_ext = ext;
-  int rc = ext ? check_taint_ids(c, ext, ids) : KSG_OK;
-  if (!rc) rc = ksg_evaluate(c, pod, ids, fail_out, score_out);
-  c->cur_ext = nullptr;
-  return rc;
-}
-
-// The read-only batch queries, each on the frame ksg_host.h describes (query_enter ...
-// query_chunks). None looks at a uid or calls note_requests: no query turns the context to the
-// int64 kernels, and later batches take the path they would have taken. A sharded context
-// covers the whole (replicated) cluster alone.
-
-// FitError reports for many pods: one grid-wide pass (ksg_explain.hip) per chunk.
-int ksg_explain_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
-                      uint32_t n_ids, uint8_t* codes, uint32_t* hist, uint8_t* err) {
-  if (!c || (n && (!pods || !hist || !err))) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  int rc;
-  if ((rc = query_enter(c, ext, n, ids, n_ids, &c->last_explain_ms))) return rc == kQueryDone ? KSG_OK : rc;
-  if ((rc = query_validate(c, pods, ext, n, ids, n_ids))) return rc;
-  const ksg_pod_ext* dext;
-  if ((rc = query_upload(c, pods, ext, n, ids, n_ids, false, &dext))) return rc;
-  // hist and err for the whole call; the per-node codes in a bounded staging buffer, a chunk
-  // of pods at a time
-  const size_t hb = (size_t)n * KSG_EXPLAIN_SLOTS * sizeof(uint32_t);
-  if ((rc = c->d_xhist.grow(c, hb + n))) return rc;
-  uint32_t* d_hist = reinterpret_cast<uint32_t*>(c->d_xhist.p);
-  uint8_t* d_err = c->d_xhist + hb;
-  HIPCHK(c, hipMemsetAsync(c->d_xhist, 0, hb + n, c->st));
-  const uint32_t per = query_per(kExplainStageBytes, codes ? c->cl.N : 0, KSG_EXPLAIN_CHUNK, n);
-  if (codes && (rc = c->d_xcodes.grow(c, (size_t)per * c->cl.N))) return rc;
-  const auto launch = [&](uint32_t a, uint32_t m) {
-    HIPCHK(c, ksg_launch_explain(c->cl.dev, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m,
-                                 codes ? c->d_xcodes : nullptr, d_hist + (size_t)a * KSG_EXPLAIN_SLOTS, d_err + a, c->st));
-    return KSG_OK;
-  };
-  const auto copies = [&](uint32_t a, uint32_t m, bool last) {
-    if (codes)
-      HIPCHK(c, hipMemcpyAsync(codes + (size_t)a * c->cl.N, c->d_xcodes, (size_t)m * c->cl.N, hipMemcpyDeviceToHost, c->st));
-    if (last) {  // straight into the caller's arrays
-      HIPCHK(c, hipMemcpyAsync(hist, d_hist, hb, hipMemcpyDeviceToHost, c->st));
-      HIPCHK(c, hipMemcpyAsync(err, d_err, n, hipMemcpyDeviceToHost, c->st));
-    }
-    return KSG_OK;
-  };
-  return query_chunks(c, n, per, &c->last_explain_ms, std::cref(launch), std::cref(copies));
-}
-
-int ksg_last_explain_ms(ksg_ctx* c, double* ms) {
-  if (!c || !ms) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  *ms = c->last_explain_ms;
-  return KSG_OK;
-}
-
-// Ranked hosts for many pods: the grid-wide reduce / score / merge passes of ksg_prioritize.hip
-// per chunk. Scores are always wrapping int64.
-int ksg_prioritize_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
-                         uint32_t n_ids, uint32_t top, int64_t* max_score, uint32_t* tie_count, uint32_t* fit_count,
-                         int32_t* top_nodes, int64_t* top_scores, int64_t* scores, uint8_t* err) {
-  if (!c || (n && (!pods || !max_score || !tie_count || !fit_count || !err))) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (top > KSG_PRIO_MAX_TOP) return fail(c, KSG_ERR_ARG, "top %u > KSG_PRIO_MAX_TOP", top);
-  if (n && top && (!top_nodes || !top_scores)) return fail(c, KSG_ERR_ARG, "top > 0 needs top_nodes and top_scores");
-  int rc;
-  if ((rc = query_enter(c, ext, n, ids, n_ids, &c->last_prioritize_ms))) return rc == kQueryDone ? KSG_OK : rc;
-  if ((rc = query_validate(c, pods, ext, n, ids, n_ids))) return rc;
-  const ksg_pod_ext* dext;  // (no records: all-zero ones, which is what ksg_evaluate scores a plain pod with)
-  if ((rc = query_upload(c, pods, ext, n, ids, n_ids, true, &dext))) return rc;
-  // the per-pod results of the whole call: int64 max[n], int64 top_scores[n][top], uint32 ties[n],
-  // uint32 fit[n], int32 top_nodes[n][top], uint8 err[n]
-  const size_t o_ts = (size_t)n * 8, o_tie = o_ts + (size_t)n * top * 8, o_fit = o_tie + (size_t)n * 4;
-  const size_t o_tn = o_fit + (size_t)n * 4, o_err = o_tn + (size_t)n * top * 4, ob = o_err + n;
-  if ((rc = c->d_pout.grow(c, ob)) || (rc = c->h_dn.grow(c, ob))) return rc;
-  uint8_t* const po = c->d_pout;
-  // pods per launch: the normalised terms, tile partials and candidates of a chunk, and its
-  // per-node scores where asked for, each within the staging budget
-  const size_t T = (c->cl.nw + KSG_PRIO_WAVES - 1) / KSG_PRIO_WAVES, D1 = (size_t)c->cl.dev.n_domains_total + 1;
-  const size_t bpp = D1 * 4 + T * (sizeof(KsgPrioPart) + (size_t)top * 12);
-  const uint32_t per = query_per(kExplainStageBytes, scores ? std::max(bpp, (size_t)c->cl.N * 8) : bpp, KSG_EXPLAIN_CHUNK, n);
-  const size_t o_part = ((size_t)per * D1 * 4 + 15) & ~(size_t)15, o_cs = o_part + (size_t)per * T * sizeof(KsgPrioPart);
-  const size_t o_cn = o_cs + (size_t)per * T * top * 8;
-  if ((rc = c->d_ppart.grow(c, o_cn + (size_t)per * T * top * 4))) return rc;
-  if (scores && (rc = c->d_pscores.grow(c, (size_t)per * c->cl.N))) return rc;
-  int32_t* const dnorm = reinterpret_cast<int32_t*>(c->d_ppart.p);
-  KsgPrioPart* const part = reinterpret_cast<KsgPrioPart*>(c->d_ppart + o_part);
-  int64_t* const cs = reinterpret_cast<int64_t*>(c->d_ppart + o_cs);
-  int32_t* const cn = reinterpret_cast<int32_t*>(c->d_ppart + o_cn);
-  const bool reduce = ksg_prio_needs_reduce(c->cl.dev, ext != nullptr);
-  const auto launch = [&](uint32_t a, uint32_t m) {
-    const ksg_pod_ext* xa = dext ? dext + a : nullptr;
-    HIPCHK(c, hipMemsetAsync(dnorm, 0, (size_t)m * D1 * 4, c->st));
-    if (reduce) HIPCHK(c, ksg_launch_prio_reduce(c->cl.dev, c->d_pods + a, xa, c->d_ids, m, dnorm, c->st));
-    HIPCHK(c, ksg_launch_prio_score(c->cl.dev, c->d_pods + a, xa, c->d_ids, m, top, dnorm,
-                                    scores ? c->d_pscores.p : nullptr, part, cs, cn, po + o_err + a, c->st));
-    HIPCHK(c, ksg_launch_prio_merge(c->cl.dev, m, top, part, cs, cn, reinterpret_cast<int64_t*>(po) + a,
-                                    reinterpret_cast<uint32_t*>(po + o_tie) + a, reinterpret_cast<uint32_t*>(po + o_fit) + a,
-                                    reinterpret_cast<int32_t*>(po + o_tn) + (size_t)a * top,
-                                    reinterpret_cast<int64_t*>(po + o_ts) + (size_t)a * top, c->st));
-    return KSG_OK;
-  };
-  const auto copies = [&](uint32_t a, uint32_t m, bool last) {
-    if (scores)
-      HIPCHK(c, hipMemcpyAsync(scores + (size_t)a * c->cl.N, c->d_pscores, (size_t)m * c->cl.N * 8, hipMemcpyDeviceToHost, c->st));
-    if (last) HIPCHK(c, hipMemcpyAsync(c->h_dn, po, ob, hipMemcpyDeviceToHost, c->st));
-    return KSG_OK;
-  };
-  rc = query_chunks(c, n, per, &c->last_prioritize_ms, std::cref(launch), std::cref(copies));
-  if (rc) return rc;
-  memcpy(max_score, c->h_dn, (size_t)n * 8);
-  memcpy(tie_count, c->h_dn + o_tie, (size_t)n * 4);
-  memcpy(fit_count, c->h_dn + o_fit, (size_t)n * 4);
-  if (top) {
-    memcpy(top_scores, c->h_dn + o_ts, (size_t)n * top * 8);
-    memcpy(top_nodes, c->h_dn + o_tn, (size_t)n * top * 4);
-  }
-  memcpy(err, c->h_dn + o_err, n);
-  return KSG_OK;
-}
-
-int ksg_last_prioritize_ms(ksg_ctx* c, double* ms) {
-  if (!c || !ms) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  *ms = c->last_prioritize_ms;
-  return KSG_OK;
-}
-
-// How many copies of each pod every node can take: one grid-wide pass (ksg_headroom.hip) per
-// chunk.
-int ksg_headroom_batch(ksg_ctx* c, const ksg_pod* pods, const ksg_pod_ext* ext, uint32_t n, const uint32_t* ids,
-                       uint32_t n_ids, uint32_t limit, uint64_t* total, uint32_t* fit_count, uint32_t* max_count,
-                       uint32_t* bind_hist, uint32_t* counts, uint8_t* err) {
-  if (!c || (n && (!pods || !total || !fit_count || !max_count || !bind_hist || !err))) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  if (limit == 0) return fail(c, KSG_ERR_ARG, "limit 0");
-  int rc;
-  if ((rc = query_enter(c, ext, n, ids, n_ids, &c->last_headroom_ms))) return rc == kQueryDone ? KSG_OK : rc;
-  if ((rc = query_validate(c, pods, ext, n, ids, n_ids))) return rc;
-  const ksg_pod_ext* dext;
-  if ((rc = query_upload(c, pods, ext, n, ids, n_ids, false, &dext))) return rc;
-  // the per-pod results of the whole call: uint64 total[n], uint32 max[n], uint32 fit[n],
-  // uint32 hist[n][KSG_HEADROOM_SLOTS], uint8 err[n]; the per-node counts in a bounded staging
-  // buffer, a chunk of pods at a time
-  const size_t o_max = (size_t)n * 8, o_fit = o_max + (size_t)n * 4, o_hist = o_fit + (size_t)n * 4;
-  const size_t hb = (size_t)n * KSG_HEADROOM_SLOTS * sizeof(uint32_t), o_err = o_hist + hb, ob = o_err + n;
-  if ((rc = c->d_hout.grow(c, ob)) || (rc = c->h_dn.grow(c, ob))) return rc;
-  uint8_t* const ho = c->d_hout;
-  HIPCHK(c, hipMemsetAsync(ho, 0, ob, c->st));
-  const uint32_t per = query_per(c->headroom_stage, counts ? (size_t)c->cl.N * sizeof(uint32_t) : 0, KSG_HEADROOM_CHUNK, n);
-  if (counts && (rc = c->d_hcounts.grow(c, (size_t)per * c->cl.N))) return rc;
-  const auto launch = [&](uint32_t a, uint32_t m) {
-    HIPCHK(c, ksg_launch_headroom(c->cl.dev, c->d_pods + a, dext ? dext + a : nullptr, c->d_ids, m, limit, c->headroom_div,
-                                  counts ? c->d_hcounts.p : nullptr, reinterpret_cast<uint64_t*>(ho) + a,
-                                  reinterpret_cast<uint32_t*>(ho + o_max) + a, reinterpret_cast<uint32_t*>(ho + o_fit) + a,
-                                  reinterpret_cast<uint32_t*>(ho + o_hist) + (size_t)a * KSG_HEADROOM_SLOTS,
-                                  ho + o_err + a, c->st));
-    return KSG_OK;
-  };
-  const auto copies = [&](uint32_t a, uint32_t m, bool last) {
-    if (counts)
-      HIPCHK(c, hipMemcpyAsync(counts + (size_t)a * c->cl.N, c->d_hcounts, (size_t)m * c->cl.N * sizeof(uint32_t),
-                               hipMemcpyDeviceToHost, c->st));
-    if (last) HIPCHK(c, hipMemcpyAsync(c->h_dn, ho, ob, hipMemcpyDeviceToHost, c->st));
-    return KSG_OK;
-  };
-  rc = query_chunks(c, n, per, &c->last_headroom_ms, std::cref(launch), std::cref(copies));
-  if (rc) return rc;
-  memcpy(total, c->h_dn, (size_t)n * 8);
-  memcpy(max_count, c->h_dn + o_max, (size_t)n * 4);
-  memcpy(fit_count, c->h_dn + o_fit, (size_t)n * 4);
-  memcpy(bind_hist, c->h_dn + o_hist, hb);
-  memcpy(err, c->h_dn + o_err, n);
-  return KSG_OK;
-}
-
-int ksg_last_headroom_ms(ksg_ctx* c, double* ms) {
-  if (!c || !ms) return KSG_ERR_ARG;
-  KSG_LOCK(c);
-  *ms = c->last_headroom_ms;
-  return KSG_OK;
 }
 
 int ksg_check_pods_exceeding_capacity(ksg_ctx* c, const ksg_admission_set* sets, uint32_t n_sets,

@@ -30,7 +30,7 @@
 //   * after idle_ticks without a request the kernel returns; the host relaunches
 //     it with the next request (every wait has that exit).
 // No stream operation can run while the server is resident: every other entry
-// point stops it first (KSG_SRV_EXIT), see ksg_runtime.cpp srv_stop.
+// point stops it first (KSG_SRV_EXIT), see ksg_dropin.cpp srv_stop.
 #include <hip/hip_runtime.h>
 #include "ksg_internal.h"
 
@@ -368,7 +368,7 @@ __global__ __launch_bounds__(KSG_NT) void ksg_serve_kernel(KsgDev d, KsgSrvArgs 
   load_totals();
 
   // KsgSrvArgs.stamps: s_memtime at the stages of each BEGIN (thread 0), written
-  // to resp[4..11] before the response (ksg_runtime.cpp sums them)
+  // to resp[4..11] before the response (ksg_dropin.cpp sums them)
   uint64_t st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   auto stamp = [&](int i) {
     if ((a.stamps & 1u) && tid == 0) st_[i] = __builtin_amdgcn_s_memtime();

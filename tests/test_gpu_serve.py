@@ -308,3 +308,104 @@ def test_serve_rejects_malformed_requests(grid, monkeypatch):
     dev.set_cluster(case.view.arrays)
     _drive(case, dev, orc, seed=1, n_pods=60, abandon=0.0)
     dev.close()
+
+
+# ---- the context's lifetime: what ksg_destroy and a refused ksg_create* release ----------
+_LIFE_SHAPES = [(900, False), (2500, True)]  # config2: the one-workgroup server, the grid server
+_LIFE_PODS = 50
+_life_refs = {}
+
+
+def _life_ref(nn):
+    """The case and, computed once per shape, the oracle's answers for its first 50 pods from an
+    empty cluster with a fixed tie sequence (fail codes wanted on every other pod), the pending
+    pod's begin after them, and the committed totals: every fresh context must repeat them."""
+    if nn not in _life_refs:
+        case = Case("config2", nn, _LIFE_PODS + 1)
+        orc = OracleScheduler(case.cfg)
+        orc.set_cluster(case.view.arrays)
+        rng = np.random.default_rng(nn)
+        steps = []
+        for i in range(_LIFE_PODS + 1):
+            rc, m, k, f = orc.begin(case.batch, i, want_fail=i % 2 == 0)
+            assert rc == abi.KSG_OK, f"pod {i}: the lifetime tests need pods that fit"
+            ix = int(rng.integers(0, k))
+            if i == _LIFE_PODS:  # the pod a context is destroyed under: never committed
+                steps.append((rc, m, k, f, ix, None))
+                break
+            steps.append((rc, m, k, f, ix, orc.commit(ix)))
+            if i == _LIFE_PODS - 1:
+                totals = orc.read_requested()
+        _life_refs[nn] = (case, steps, totals)
+    return _life_refs[nn]
+
+
+def _life_fifty(dev, case, steps):
+    """50 served begin / commit pods equal to the oracle's; the last call is a commit."""
+    for i in range(_LIFE_PODS):
+        rc, m, k, f, ix, node = steps[i]
+        rg, mg, kg, fg = dev.begin(case.batch, i, want_fail=f is not None)
+        assert (rg, mg, kg) == (rc, m, k), f"pod {i}: gpu {(rg, mg, kg)} oracle {(rc, m, k)}"
+        if f is not None:
+            assert np.array_equal(fg, f), f"pod {i}: fail codes"
+        assert dev.commit(ix) == node, f"pod {i}: node"
+
+
+def _life_served(dev, grid):
+    st = dev.serve_stats()
+    assert st["eligible"] and st["grid"] == grid and st["launches"] >= 1, st
+    assert st["requests"] >= 2 * _LIFE_PODS, st  # (every begin and commit was a request)
+
+
+@pytest.mark.parametrize("nn,grid", _LIFE_SHAPES)
+def test_serve_context_lifetime(nn, grid, monkeypatch):
+    """Three contexts one after the other in one process, each serving the same 50 pods as the
+    oracle: the first is destroyed with a served begin pending, the second right after a commit
+    whose answer was not awaited (ksg_destroy stops the server, waits for the stream and lets the
+    context's members free what they own), and the third still schedules like the oracle."""
+    monkeypatch.setenv("KSG_SERVE_GRID", "1" if grid else "0")
+    case, steps, totals = _life_ref(nn)
+    for end in ("pending", "commit", "read"):
+        dev = DeviceScheduler(case.cfg, device=0)
+        dev.set_cluster(case.view.arrays)
+        _life_fifty(dev, case, steps)
+        if end == "pending":
+            rc, m, k, _, _, _ = steps[_LIFE_PODS]
+            assert dev.begin(case.batch, _LIFE_PODS)[:3] == (rc, m, k)
+        _life_served(dev, grid)  # (reads the client's counters: no request, no wait)
+        if end == "read":
+            gc, gm = dev.read_requested()
+            assert np.array_equal(gc, totals[0]) and np.array_equal(gm, totals[1])
+        dev.close()
+
+
+def _max_world():
+    import os
+    import re
+
+    hdr = os.path.join(os.path.dirname(abi.__file__), "csrc", "ksg_internal.h")
+    with open(hdr) as fh:
+        return int(re.search(r"^#define KSG_MAX_WORLD (\d+)$", fh.read(), re.M).group(1))
+
+
+@pytest.mark.parametrize("nn,grid", _LIFE_SHAPES)
+def test_serve_after_refused_create(nn, grid, monkeypatch):
+    """ksg_create_sharded refuses a world above KSG_MAX_WORLD (no nccl_id) with KSG_ERR_ARG and no
+    context, after it has made the stream and its events: eight refusals, each releasing its
+    half-built context, then an ordinary context on the same device schedules like the oracle."""
+    import ctypes as C
+
+    monkeypatch.setenv("KSG_SERVE_GRID", "1" if grid else "0")
+    case, steps, totals = _life_ref(nn)
+    lib = abi.load_library()
+    for _ in range(8):
+        ctx = C.c_void_p()
+        rc = lib.ksg_create_sharded(C.byref(case.cfg), 0, 0, _max_world() + 1, None, C.byref(ctx))
+        assert rc == abi.KSG_ERR_ARG and not ctx.value
+    dev = DeviceScheduler(case.cfg, device=0)
+    dev.set_cluster(case.view.arrays)
+    _life_fifty(dev, case, steps)
+    _life_served(dev, grid)
+    gc, gm = dev.read_requested()
+    assert np.array_equal(gc, totals[0]) and np.array_equal(gm, totals[1])
+    dev.close()
